@@ -7,8 +7,21 @@ int32 cost table (97840 entries per CTU, the reference's minSadHad table).  Fram
 across GPUs (one process per GPU, no data-path collective; RCCL only carries the barrier
 and the max-over-ranks of the timing) -> weak scaling.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames-per-step B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames-per-step B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, write
+the outputs (`--dump-outputs DIR`) and print the line.  `--full` adds every other measurement
+listed below that takes launches or processes of its own (filter, single_frame_ms,
+decisions_device, cpu_baseline, reference_gpu, end_to_end); the `--no-*` options drop single
+ones of them again.
+
+`--dump-outputs DIR` writes what the last timed step left in the cost table as float64 .npy
+files (same arguments, same frames, so two builds can be compared entry for entry):
+  cost_ctu_sums.npy    [B, CTUs per frame] sum of each CTU's 97840 costs (exact: < 2^53);
+  cost_sample.npy      DUMP_SAMPLE entries of the table at cost_sample_index.npy's flat
+                       positions (a fixed seeded sample: the whole table is 20 GB at B = 384).
+Ranks of a multi-GPU run write their own shard's files with a `_rank<r>` suffix.
 
 Without a launcher (WORLD_SIZE unset), `--gpus N` > 1 starts the N ranks itself (one child
 process per GPU, before anything touches the GPU) and exits with their status; under a
@@ -63,6 +76,8 @@ VECTOR_OPS_PER_CTU = 99.6e6
 E2E_CALLS = 8  # host-buffer calls queued per end-to-end measurement round
 E2E_ROUNDS = 3  # timed rounds per end-to-end leg (median reported)
 E2E_FRAMES_MULTI = 32  # frames per host-buffer call at N > 1 (bounds each rank's page-locked memory)
+DUMP_SAMPLE = 1 << 21  # cost-table entries --dump-outputs samples (16 MiB as float64, as much again for the index)
+DUMP_SEED = 0xD0C5     # seed of that sample's positions (fixed: the same positions in every run)
 
 
 def metric_name(width, height):
@@ -447,6 +462,30 @@ def e2e_multi_section(legs, world, coll_dev, frames_per_call, note):
     return res
 
 
+def dump_positions(total):
+    """Flat positions of the cost-table sample: every entry of a table of at most DUMP_SAMPLE
+    entries, else DUMP_SAMPLE sorted positions drawn with a fixed seed."""
+    import numpy as np
+    if total <= DUMP_SAMPLE:
+        return np.arange(total, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).integers(0, total, size=DUMP_SAMPLE, dtype=np.int64))
+
+
+def dump_outputs(path, costs, ctus, rank, world):
+    """--dump-outputs: the cost table of the last timed step ([B, costs per frame] int32 on the
+    device) as float64 .npy files (see the module docstring)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    tag = "" if world == 1 else "_rank%d" % rank
+    sums = costs.view(costs.shape[0], ctus, -1).sum(dim=2, dtype=torch.int64)
+    pos = dump_positions(costs.numel())
+    sample = costs.view(-1)[torch.from_numpy(pos).to(costs.device)]
+    np.save(os.path.join(path, "cost_ctu_sums%s.npy" % tag), sums.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "cost_sample%s.npy" % tag), sample.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "cost_sample_index%s.npy" % tag), pos.astype(np.float64))
+
+
 def plumbing_check(args):
     """--plumbing-check: the multi-rank path of main() on CPU (gloo), a sleep per step."""
     import torch.distributed as dist
@@ -466,7 +505,7 @@ def plumbing_check(args):
     value, ms_per_step = aggregate(args.frames_per_step, args.steps, world, max_elapsed)
     # the end-to-end legs' aggregation at N > 1 (a sleep per round; rank r the (r+1)-times slower)
     e2e = None
-    if world > 1 and not args.no_end_to_end:
+    if world > 1 and args.full and not args.no_end_to_end:
         legs = {"value": timed_rounds(lambda: time.sleep(0.01 * (1 + rank)), world, None, E2E_CALLS * E2E_FRAMES_MULTI),
                 "decisions_value": timed_rounds(lambda: time.sleep(0.005 * (1 + rank)), world, None,
                                                 E2E_CALLS * E2E_FRAMES_MULTI)}
@@ -493,6 +532,12 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x1080)
     ap.add_argument("--slices", type=int, default=0, help="workgroups per CTU (0 = engine default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline figure (filter, latency, decisions, CPU "
+                         "baseline, reference kernels, end to end); the --no-* options drop single ones")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's cost table (per-CTU sums and a fixed seeded sample) as "
+                         "float64 .npy files into DIR")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-reference-gpu", action="store_true")
     ap.add_argument("--no-latency", action="store_true", help="skip the single-frame latency launches")
@@ -573,9 +618,11 @@ def main():
     max_elapsed = max(r[0] for r in per_rank)
     max_kernel_ms = max(r[1] for r in per_rank)
     value, ms_per_step = aggregate(B, args.steps, world, max_elapsed)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, costs, num_ctus(W, H), rank, world)
 
     e2e_multi = None
-    if world > 1 and not args.no_end_to_end:
+    if world > 1 and args.full and not args.no_end_to_end:
         # Host-fed rate of the whole job (informative, never `value`): every rank feeds its own
         # GPU from page-locked host buffers on that GPU's NUMA node -- E2E_CALLS asynchronous
         # calls of E2E_FRAMES_MULTI frames per round, rounds aligned by a barrier and timed by
@@ -646,9 +693,10 @@ def main():
         if knobs:
             res["knobs"] = knobs
             res["headline"] = False  # measured with work knobs set (A/B tooling)
-        if world == 1 and not args.no_filter:
+        extras = world == 1 and args.full  # the measurements beside the headline figure
+        if extras and not args.no_filter:
             res["filter"] = filter_section(MipEngine, frames, W, H, B, stream, dev, 5, pmc)
-        if world == 1 and not args.no_latency:
+        if extras and not args.no_latency:
             # Latency of a single-frame launch (informative; `value` is batch throughput).
             f1 = torch.empty((1, eng.costs_per_frame), dtype=torch.int32, device=dev)
             for _ in range(3):
@@ -660,7 +708,7 @@ def main():
             e1.record(stream)
             torch.cuda.synchronize(dev)
             res["single_frame_ms"] = round(e0.elapsed_time(e1) / 20, 4)
-        if world == 1 and not args.no_latency:
+        if extras and not args.no_latency:
             # Decisions only (the serving path): the same B resident frames, no cost table --
             # the per-CU argmin is fused into the search (mip_search_device with d_costs NULL).
             bm = torch.empty((B, eng.cus_per_frame), dtype=torch.uint8, device=dev)
@@ -676,13 +724,13 @@ def main():
             res["decisions_device"] = {"value": round(5 * B / (e0.elapsed_time(e1) * 1e-3), 1), "unit": "frames/s",
                                        "note": "per-CU best mode + cost of the same resident frames, no cost table "
                                                "(argmin fused into the search kernel), device time"}
-        if world == 1:
+        if extras:
             if not args.no_cpu_baseline:
                 res["cpu_baseline"] = cpu_baseline(W, H, args.seed)
                 rk = reference_kernels_cpu(W, H, args.seed)
                 if rk is not None:
                     res["cpu_baseline"]["reference_kernels"] = rk
-        if world == 1 and not args.no_end_to_end:
+        if extras and not args.no_end_to_end:
             # Host-buffer path incl. PCIe (informative, never `value`): page-locked buffers
             # (mip_host_alloc; transfers overlap the next chunk's search) and pageable ones.
             # Each leg: one warm-up round, then E2E_ROUNDS timed rounds of E2E_CALLS
@@ -737,7 +785,7 @@ def main():
                                          "(%.1f MB per frame)" %
                                          (algorithmic_bytes_per_frame(W, H) / 1e6, E2E_CALLS, Be, E2E_ROUNDS,
                                           (2 * W * H + 5 * eng.cus_per_frame) / 1e6)}
-        if world == 1 and not args.no_reference_gpu:
+        if extras and not args.no_reference_gpu:
             ref = reference_gpu(W, H, min(B, 4), args.seed)
             if ref is not None:
                 res["reference_gpu"] = ref

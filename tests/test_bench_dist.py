@@ -61,7 +61,7 @@ def test_gpus_flag_without_launcher_starts_ranks():
     import subprocess
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, bench.__file__, "--gpus", "2", "--plumbing-check", "--steps", "5",
+    r = subprocess.run([sys.executable, bench.__file__, "--gpus", "2", "--plumbing-check", "--full", "--steps", "5",
                         "--frames-per-step", "4"], capture_output=True, text=True, timeout=180, env=env)
     assert r.returncode == 0, r.stderr
     line = json.loads(r.stdout.strip().splitlines()[-1])

@@ -2,6 +2,7 @@
 completion-thread logic over a simulated device (tests/cpp/test_host_stage.cpp), built with
 g++ (no GPU), and once more under ThreadSanitizer on a smaller workload."""
 import os
+import platform
 import shutil
 import subprocess
 
@@ -33,8 +34,21 @@ def test_host_stage_thread_sanitizer(tmp_path):
         _build(exe, ["-g", "-fsanitize=thread"])
     except subprocess.CalledProcessError:
         pytest.skip("compiler without ThreadSanitizer")
-    r = subprocess.run([str(exe), "quick"], capture_output=True, text=True, timeout=180,
-                       env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1"))
+    def run(prefix):
+        return subprocess.run(prefix + [str(exe), "quick"], capture_output=True, text=True, timeout=180,
+                              env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1"))
+
+    # Where the kernel randomises mappings over more address bits than this ThreadSanitizer
+    # runtime knows, the runtime ends before main() with this message, on some starts or on all:
+    # then once more with address randomisation off, and no verdict where that does not help.
+    no_shadow = "FATAL: ThreadSanitizer: unexpected memory mapping"
+    r = run([])
+    if no_shadow in r.stderr and shutil.which("setarch"):
+        again = run(["setarch", platform.machine(), "-R"])
+        if again.returncode == 0 or "ThreadSanitizer" in again.stderr:  # (else setarch itself was refused)
+            r = again
+    if no_shadow in r.stderr:
+        pytest.skip("ThreadSanitizer's runtime cannot place its shadow memory on this kernel: " + r.stderr.strip()[-200:])
     assert r.returncode == 0, r.stdout + r.stderr[-4000:]
     assert "ThreadSanitizer" not in r.stderr, r.stderr[-4000:]
     assert "host_stage: ok" in r.stdout

@@ -1,4 +1,6 @@
 """Static tables: the generated header / Python table vs the reference's constants."""
+import hashlib
+import json
 import os
 import subprocess
 import sys
@@ -42,7 +44,6 @@ def test_best_modes_numpy():
     assert m[0] == np.argmin(row) and v[0] == row.min()
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="reference tree not mounted")
 def test_topk_numpy_statement():
     """layout.topk_modes: stable ordering, padding past a CU's modes, unavailable CUs."""
     rng = np.random.default_rng(5)
@@ -61,25 +62,51 @@ def test_topk_numpy_statement():
     assert (np.diff(v[:, :12].astype(np.int64), axis=1) >= 0).all()
 
 
-def test_generated_header_matches_reference():
-    """Re-derive the tables from the reference files and compare with the committed ones."""
+FACTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tables", "reference_tables.json")
+
+
+def _sha(values):
+    return hashlib.sha256(json.dumps([int(v) for v in values]).encode()).hexdigest()
+
+
+def reference_facts():
+    """What the table test needs of the reference's files, derived from the reference tree: the
+    header tools/gen_tables.py renders from them and the tables it is checked against, each as
+    a SHA-256 (of the header's text, of json.dumps of a table's list of ints).  Recorded in
+    tests/golden/tables/reference_tables.json (`python tests/test_tables.py` where the tree is)."""
     sys.path.insert(0, TOOLS)
     from gen_tables import render
-    text, offs, c = render()
-    hdr = os.path.join(os.path.dirname(TOOLS), "vvc-mip-gpu_amd", "csrc", "mip_tables.h")
-    assert open(hdr).read() == text
-    assert offs + [97840] == c["ALL_stridedDistortionsPerCtu"]
-    # Positions re-expanded from the lattice description == ALL_X_POS / ALL_Y_POS rows.
     from refparse import parse_rows
+    text, _, c = render()
+    n = c["ALL_cusPerCtu"]
     X = parse_rows(REF + "/constants.cl", "ALL_X_POS")
     Y = parse_rows(REF + "/constants.cl", "ALL_Y_POS")
+    facts = {"mip_tables_h": hashlib.sha256(text.encode()).hexdigest(),
+             "ALL_X_POS": [_sha(X[i][:n[i]]) for i in range(46)],
+             "ALL_Y_POS": [_sha(Y[i][:n[i]]) for i in range(46)]}
+    for name in ("ALL_stridedDistortionsPerCtu", "ALL_widths", "ALL_heights", "ALL_cusPerCtu", "ALL_numPredModes"):
+        facts[name] = _sha(c[name])
+    return facts
+
+
+def test_generated_header_matches_reference():
+    """The committed tables against the reference's, through the recorded hashes of the
+    reference's tables (and, where the reference tree is present, those hashes re-derived)."""
+    facts = json.load(open(FACTS))
+    if HAVE_REF:
+        assert reference_facts() == facts
+    hdr = os.path.join(os.path.dirname(TOOLS), "vvc-mip-gpu_amd", "csrc", "mip_tables.h")
+    assert hashlib.sha256(open(hdr, "rb").read()).hexdigest() == facts["mip_tables_h"]
+    offs = [s.cost_offset for s in layout.SHAPES]
+    assert _sha(offs + [97840]) == facts["ALL_stridedDistortionsPerCtu"]
+    # Positions re-expanded from the lattice description == ALL_X_POS / ALL_Y_POS rows.
     for s in layout.SHAPES[:46]:
         x, y = s.positions()
-        assert list(x) == X[s.index][:s.ncu] and list(y) == Y[s.index][:s.ncu], s.name
-    assert [s.w for s in layout.SHAPES] == c["ALL_widths"]
-    assert [s.h for s in layout.SHAPES] == c["ALL_heights"]
-    assert [s.ncu for s in layout.SHAPES] == c["ALL_cusPerCtu"]
-    assert [s.modes for s in layout.SHAPES] == c["ALL_numPredModes"]
+        assert _sha(x) == facts["ALL_X_POS"][s.index] and _sha(y) == facts["ALL_Y_POS"][s.index], s.name
+    assert _sha(s.w for s in layout.SHAPES) == facts["ALL_widths"]
+    assert _sha(s.h for s in layout.SHAPES) == facts["ALL_heights"]
+    assert _sha(s.ncu for s in layout.SHAPES) == facts["ALL_cusPerCtu"]
+    assert _sha(s.modes for s in layout.SHAPES) == facts["ALL_numPredModes"]
 
 
 def _taps(name):
@@ -111,3 +138,9 @@ def test_torch_synth_matches_numpy_generator():
         b = synth_frames_torch(136, 72, 2, seed, kind).numpy().astype(np.uint16)
         assert np.array_equal(a, b), (kind, seed)
 
+
+if __name__ == "__main__":  # PYTHONPATH=vvc-mip-gpu_amd python tests/test_tables.py (needs the reference tree)
+    with open(FACTS, "w") as f:
+        json.dump(reference_facts(), f, indent=1)
+        f.write("\n")
+    print("wrote", FACTS)

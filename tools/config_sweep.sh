@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 mkdir -p "${OUT:-gpurun_out}"
 OUT=${OUT:-gpurun_out}/configs.jsonl
 : > "$OUT"
-COMMON="--no-cpu-baseline --no-reference-gpu --no-latency --no-filter --steps 10 --warmup 2"
+COMMON="--full --no-cpu-baseline --no-reference-gpu --no-latency --no-filter --steps 10 --warmup 2"
 run() { echo "== $*" >&2; timeout -k 10 300 python bench.py $COMMON "$@" >> "$OUT"; }
 run --frames-per-step 1                                   # configs[1]: 1 x 1080p, original refs
 run --frames-per-step 2 --refs-filter filterFrame_2d_float_5x5_quarterCtu --kernel-idx 2   # configs[2]

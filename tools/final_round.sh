@@ -32,7 +32,7 @@ json.dump(d, open(out + "/traffic.json", "w"), indent=1)
 print("traffic.json:", {k: v.get("build_id") for k, v in new.items()})
 PY
 step bench
-timeout -k 10 900 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+timeout -k 10 900 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
 cat "$OUT/bench.json"
 step small_batch
 SB_CUTS=2 SB_ORDERS=1 SB_SLICES=0 timeout -k 10 300 python -u tools/small_batch.py > "$OUT/small.jsonl" 2> "$OUT/small.err" \

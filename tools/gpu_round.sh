@@ -19,13 +19,13 @@ step ref_runner
 timeout -k 10 300 oracle/_ref/ref_runner --bins oracle/_ref --width 1920 --height 1080 --frames 4 --synth 0:1080 --reps 2 > "$OUT/ref_timing.json" 2>&1 || { cat "$OUT/ref_timing.json"; exit 1; }
 cat "$OUT/ref_timing.json"
 step bench
-timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
 cat "$OUT/bench.json"
 [ -n "${SKIP_PROF:-}" ] && { step done; exit 0; }
 step rocprof
 rm -rf "$OUT/prof"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
-  python bench.py --no-cpu-baseline --no-reference-gpu --no-latency --no-end-to-end --steps 10 > "$OUT/prof_bench.json" 2> "$OUT/prof.err" \
+  python bench.py --full --no-cpu-baseline --no-reference-gpu --no-latency --no-end-to-end --steps 10 > "$OUT/prof_bench.json" 2> "$OUT/prof.err" \
   || { tail -20 "$OUT/prof.err"; exit 1; }
 find "$OUT/prof" -name "*stats*" | head
 step done

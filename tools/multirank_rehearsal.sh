@@ -8,11 +8,11 @@ cd "$(dirname "$0")/.."
 OUT=${OUT:-gpurun_out}/multirank
 mkdir -p "$OUT"
 # (round 6: the end-to-end legs run on every rank at N > 1 -- end_to_end.aggregate)
-ARGS="--frames-per-step 128 --steps 10 --warmup 2 --no-cpu-baseline --no-reference-gpu --no-latency --no-filter"
+ARGS="--full --frames-per-step 128 --steps 10 --warmup 2 --no-cpu-baseline --no-reference-gpu --no-latency --no-filter"
 ARGS1="$ARGS --no-end-to-end"
 # the driver's 8-GPU launch shape, rehearsed with 8 ranks on this box's one device (round 5:
 # launcher, rendezvous, `ranks`, max over 8 ranks; 32 frames per rank keep 8 engines in HBM)
-ARGS8="--frames-per-step 32 --steps 10 --warmup 2 --no-cpu-baseline --no-reference-gpu --no-latency --no-filter"
+ARGS8="--full --frames-per-step 32 --steps 10 --warmup 2 --no-cpu-baseline --no-reference-gpu --no-latency --no-filter"
 echo "== bench --gpus 8 (own ranks, 8 ranks sharing device 0) $(date +%T)"
 timeout -k 10 400 python bench.py --gpus 8 $ARGS8 > "$OUT/bench_gpus8.json" 2> "$OUT/bench_gpus8.err" || { tail -20 "$OUT/bench_gpus8.err"; exit 1; }
 cat "$OUT/bench_gpus8.json"

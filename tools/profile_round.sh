@@ -13,7 +13,7 @@ RAW=/tmp/prof_raw
 rm -rf "$RAW"
 mkdir -p "$OUT" "$RAW"
 export TMPDIR=/tmp
-ARGS="--no-cpu-baseline --no-reference-gpu --no-latency --no-end-to-end $*"
+ARGS="--full --no-cpu-baseline --no-reference-gpu --no-latency --no-end-to-end $*"
 FRAMES=$(python3 -c "import sys; a=sys.argv[1:]; print(a[a.index('--frames-per-step')+1] if '--frames-per-step' in a else 384)" $ARGS)
 echo "== kernel trace $(date +%T)"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$RAW/trace" -o run --output-format csv -- \
