@@ -212,6 +212,74 @@ int mip_search_device_range(mip_engine *e, const uint16_t *d_frames, const uint1
 int mip_topk_device(const int32_t *d_costs, int width, int height, int nframes, int k,
                     uint8_t *d_modes, int32_t *d_costs_k, void *stream);
 
+/* Prediction output (additive to ABI 7; no reference counterpart -- the reference's
+ * upsampleDistortion builds the predicted samples in local memory, measures them and drops
+ * them, intra.cl:545-1166): the predicted samples of chosen (CU, mode) pairs, what an encoder
+ * needs after the decision (residual, the full-RD stage on mip_topk_device's candidates, a
+ * predicted frame).  The stages are the reference's: boundaries with linear indexes and padding
+ * (intra.cl:96-107, 232-243, 127-141, 259-279), the matrix product with transposition
+ * (intra.cl:415-485), horizontal then vertical upsampling (intra.cl:815-912) -- so the SAD /
+ * SATD of an emitted block against the original samples are the entries of the SAD / SATD
+ * tables.
+ *
+ * A list item names a frame of the call, a CU and a mode, and says where its w x h samples go
+ * in the output buffer `out` of out_samples uint16: row r of the block at
+ * out[offset + r*pitch .. + w).  mip_pred_layout fills pitch / offset for the two usual
+ * layouts; callers may set their own.
+ *
+ * Write rule.  An item is written only when ALL of these hold:
+ *   - 0 <= frame < nframes and 0 <= cu < nCTUs*5380;
+ *   - the CU is available for this engine, i.e. not in mip_unavailable_cus(width, height,
+ *     filter) (with caller-supplied references: the MIP_FILTER_NONE set);
+ *   - 0 <= mode < 2*modes of the CU's shape;
+ *   - pitch >= w; pitch and offset are multiples of 4 samples; offset >= 0;
+ *   - offset + (h-1)*pitch + w <= out_samples.
+ * Any other item writes nothing and reads no sample; it is counted in the skipped counter.
+ * The device kernel checks every item itself: a device-side list is data, and a bad entry
+ * never becomes an out-of-bounds access.  Items whose blocks overlap in `out` (a frame layout
+ * with CUs of several shapes, wrapped CUs) are the caller's business: which one wins is
+ * unspecified. */
+typedef struct {
+  int32_t frame;   /* 0 .. nframes-1 */
+  int32_t cu;      /* ctu*5380 + shape CU prefix + cu: the index used by best_mode_out */
+  int32_t mode;    /* 0 .. 2*modes-1, numbered as the log's Mode column; anything else (0xff) = none */
+  int32_t pitch;   /* samples between consecutive rows of the block in `out` */
+  int64_t offset;  /* sample index in `out` of the block's top-left sample */
+} mip_pred_item;   /* 24 bytes */
+
+#define MIP_PRED_PACKED 0   /* blocks back to back, row-major w x h, list order (pitch = w) */
+#define MIP_PRED_FRAME  1   /* blocks at their place in frame-shaped canvases: pitch = width,
+                               offset = frame*W*H + y*W + x, the reference's linear addressing
+                               (CUs right of the frame wrap into the next row; every available
+                               CU stays inside its frame) */
+#define MIP_PRED_NONE 0xffff
+
+/* Fill pitch and offset of `n` items (frame, cu set by the caller) for `layout` and return the
+ * output size in *out_samples.  Packed: offset = exclusive prefix sum of w*h in list order
+ * (items with mode "none" and unavailable CUs reserve their block too).  Frame: out_samples =
+ * nframes*W*H.  Host only (no HIP call).  <0 for a frame or cu out of range. */
+int mip_pred_layout(int width, int height, int nframes, int layout,
+                    mip_pred_item *items, int64_t n, int64_t *out_samples);
+
+/* Predict the items of a device list into d_out (8-byte aligned, as d_items), asynchronous on
+ * `stream`.  Reference source as in mip_search_device: d_refs NULL = the originals, or the
+ * engine's filter applied into engine scratch (nframes <= max_batch then); otherwise the
+ * caller's frames.  Samples of d_out that no item writes are left as they were.  d_skipped:
+ * optional device word, zeroed by the caller, incremented once per item not written. */
+int mip_predict_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes,
+                       const mip_pred_item *d_items, int64_t n, uint16_t *d_out, int64_t out_samples,
+                       uint32_t *d_skipped, void *stream);
+
+/* Synchronous host variant: uploads, filters if the engine has a filter and no references are
+ * given, predicts, downloads (no pipelining).  Like mip_filter_frames it first waits for every
+ * call in flight (an open merged chunk is launched).  The list is validated on the host: a
+ * frame or cu out of range fails the call; items the write rule excludes otherwise are skipped.
+ * Samples of `out` that no item writes are MIP_PRED_NONE; *skipped (optional) receives the
+ * number of items not written.  With refs the originals are not read (frames may be NULL). */
+int mip_predict_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
+                       const mip_pred_item *items, int64_t n, uint16_t *out, int64_t out_samples,
+                       int64_t *skipped);
+
 /* Streaming device-to-device copy of `bytes` (a multiple of 16, 16-byte aligned pointers),
  * asynchronous on `stream`: 16 bytes per lane, four loads in flight per lane -- the HBM copy
  * rate bench.py prices the filter kernel against (no reference counterpart). */

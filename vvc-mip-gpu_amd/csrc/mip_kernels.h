@@ -1,8 +1,11 @@
 // mip_kernels.h -- launch interface between the C-ABI host code (mipgpu.cpp) and the
-// gfx950 kernels (mip_search.hip, mip_filter.hip).  Not part of the public ABI.
+// gfx950 kernels (mip_search.hip, mip_filter.hip, mip_fixup.hip, mip_predict.hip).  Not part
+// of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "mipgpu.h"  // mip_pred_item
 
 namespace mipgpu {
 
@@ -245,5 +248,21 @@ hipError_t launch_gather_copy(const CopyPieces &a, hipStream_t s);
 // Exact per-CU search of `n` CUs of every frame (same outputs as the search kernel: cost /
 // SAD / SATD tables or, decisions only, the decision in a.best_mode / a.best_cost).
 hipError_t launch_fixup(const SearchArgs &a, const FixupCu *cus, int n, int nframes, hipStream_t s);
+
+// Prediction output (predict_kernel): the samples of `n` list items, each checked by the
+// kernel against the write rule of include/mipgpu.h.
+struct PredictArgs {
+  const uint16_t *refs;       // [nframes][height][width] reference-sample source
+  const mip_pred_item *items; // device list
+  long long n;                // items, <= 2^31 - 256
+  const uint8_t *unavail;     // [nctus * 5380] 1 = the CU is not predicted (mip_unavailable_cus)
+  const uint32_t *geo;        // [5380] CU inside the CTU: shape | x << 8 | y << 16
+  uint16_t *out;              // 8-byte aligned
+  long long out_samples;
+  uint32_t *skipped;          // optional: items that were not written are counted here
+  int width, height, ctu_cols, nctus, nframes;
+  int refs_vec;               // refs is 8-byte aligned: top rows are read 4 samples per load
+};
+hipError_t launch_predict(const PredictArgs &a, hipStream_t s);
 
 }  // namespace mipgpu

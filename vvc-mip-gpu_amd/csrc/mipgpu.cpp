@@ -205,6 +205,26 @@ bool cu_defined(int width, int height, int x, int y, int w, int h) {
   return y + h <= height && (long long)(y + h - 1) * width + x + w - 1 < (long long)width * height;
 }
 
+// CU inside the CTU (reference order, 0..5379) -> its shape and CTU-relative position
+// (prediction lists name CUs by this index, like the decision lists).
+struct CuGeo {
+  uint8_t shape, x, y;
+};
+const std::vector<CuGeo> &cu_geo_table() {
+  static const std::vector<CuGeo> table = [] {
+    std::vector<CuGeo> t;
+    t.reserve(MIP_CUS_PER_CTU);
+    for (int s = 0; s < MIP_NUM_SHAPES; s++) {
+      const mip_shape_desc &sd = kShapes[s];
+      for (int cu = 0; cu < sd.ncu; cu++)
+        t.push_back(CuGeo{(uint8_t)s, (uint8_t)axis_pos(sd.xb, sd.xs, sd.xd, cu % sd.ncols),
+                          (uint8_t)axis_pos(sd.yb, sd.ys, sd.yd, cu / sd.ncols)});
+    }
+    return t;
+  }();
+  return table;
+}
+
 // Reference samples above 10 bits.  At widths that are not multiples of 128 the reference's
 // separable filters give the last one or two frame columns values up to ~1.7 x 1023: the
 // horizontal pass there sums the wrapped next-row samples while the scale is the frame-edge
@@ -582,6 +602,12 @@ struct mip_engine {
                                             // caller refs / engine-filtered refs)
   mipgpu::FixupCu *d_fixup[kMaps] = {};     // alt refs: CUs of the exact per-CU kernel, per map
   int nfixup[kMaps] = {};
+  // Prediction output (mip_predict_device), uploaded at its first use: the CUs that are not
+  // predicted, [0] with caller-supplied or original references (the MIP_FILTER_NONE set of
+  // mip_unavailable_cus), [1] with the engine filter's references (== [0] without a filter);
+  // and the CU geometry inside a CTU (PredictArgs::geo).
+  uint8_t *d_pred_unavail[2] = {};
+  uint32_t *d_pred_geo = nullptr;
   int resident[2] = {0, 0};  // persistent search grid (workgroups resident on this device), [alt]
   int resident_wide[2] = {0, 0};  // the same for 16-wave workgroups
   int resident_four[2] = {0, 0};  // the four-wave twin's (8-wave workgroups; 0: not available)
@@ -1033,6 +1059,9 @@ int mip_engine_destroy(mip_engine *e) {
     dev_free(e->d_ctu_var[m]);
     dev_free(e->d_fixup[m]);
   }
+  if (e->d_pred_unavail[1] != e->d_pred_unavail[0]) dev_free(e->d_pred_unavail[1]);
+  dev_free(e->d_pred_unavail[0]);
+  dev_free(e->d_pred_geo);
   dev_free(e->d_queue);
   if (e->h_status) (void)hipHostFree(e->h_status);
   if (e->h_frame_status) (void)hipHostFree(e->h_frame_status);
@@ -2194,6 +2223,211 @@ int mip_filter_frames(mip_engine *e, const uint16_t *frames, int nframes, int fi
   HIP_TRY(hipStreamSynchronize(e->stream2));
   e->refs_pending = false;
   return 0;
+}
+
+// ---------------------------------------------------------------- prediction output
+int mip_pred_layout(int width, int height, int nframes, int layout, mip_pred_item *items, int64_t n,
+                    int64_t *out_samples) {
+  if (width <= 0 || height <= 0 || width % 4 || height % 4 || nframes < 1 || n < 0 || (n && !items) || !out_samples)
+    return fail("bad prediction-layout arguments");
+  if (layout != MIP_PRED_PACKED && layout != MIP_PRED_FRAME) return fail("unknown prediction layout %d", layout);
+  const std::vector<CuGeo> &geo = cu_geo_table();
+  const int cols = (width + 127) / 128, ncus = mip_num_ctus(width, height) * MIP_CUS_PER_CTU;
+  const int64_t fs = (int64_t)width * height;
+  int64_t next = 0;
+  for (int64_t i = 0; i < n; i++) {
+    mip_pred_item &it = items[i];
+    if (it.frame < 0 || it.frame >= nframes)
+      return fail("prediction item %lld: frame %d outside 0..%d", (long long)i, it.frame, nframes - 1);
+    if (it.cu < 0 || it.cu >= ncus) return fail("prediction item %lld: cu %d outside 0..%d", (long long)i, it.cu, ncus - 1);
+    const int ctu = it.cu / MIP_CUS_PER_CTU;
+    const CuGeo &g = geo[(size_t)(it.cu % MIP_CUS_PER_CTU)];
+    const mip_shape_desc &sd = kShapes[g.shape];
+    if (layout == MIP_PRED_PACKED) {
+      it.pitch = sd.w;
+      it.offset = next;
+      next += (int64_t)sd.w * sd.h;
+    } else {
+      it.pitch = width;
+      it.offset = it.frame * fs + (int64_t)(128 * (ctu / cols) + g.y) * width + 128 * (ctu % cols) + g.x;
+    }
+  }
+  *out_samples = layout == MIP_PRED_PACKED ? next : (int64_t)nframes * fs;
+  return 0;
+}
+
+// The engine's prediction tables (mip_engine::d_pred_unavail, d_pred_geo), uploaded once.
+static int ensure_pred_tables(mip_engine *e) {
+  if (e->d_pred_geo) return 0;
+  const size_t ncus = (size_t)e->nctus * MIP_CUS_PER_CTU;
+  std::vector<uint8_t> un(ncus);
+  for (int m = 0; m < 2; m++) {
+    if (m == 1 && e->opts.filter == MIP_FILTER_NONE) {
+      e->d_pred_unavail[1] = e->d_pred_unavail[0];
+      break;
+    }
+    if (mip_unavailable_cus(e->width, e->height, m ? e->opts.filter : MIP_FILTER_NONE, un.data()) != 0) return -1;
+    HIP_TRY(dev_malloc(e->device, (void **)&e->d_pred_unavail[m], ncus));
+    HIP_TRY(hipMemcpy(e->d_pred_unavail[m], un.data(), ncus, hipMemcpyHostToDevice));
+  }
+  const std::vector<CuGeo> &geo = cu_geo_table();
+  std::vector<uint32_t> packed(geo.size());
+  for (size_t i = 0; i < geo.size(); i++) packed[i] = geo[i].shape | (uint32_t)geo[i].x << 8 | (uint32_t)geo[i].y << 16;
+  uint32_t *d = nullptr;
+  HIP_TRY(dev_malloc(e->device, (void **)&d, packed.size() * sizeof(uint32_t)));
+  if (hipMemcpy(d, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+    dev_free(d);
+    return fail("uploading the CU geometry failed");
+  }
+  e->d_pred_geo = d;  // (set last: the tables are complete)
+  return 0;
+}
+
+// refs: the reference frames to predict from (already resolved); engine_refs: they are the
+// engine filter's output (its unavailable set applies).
+static int predict_launch(mip_engine *e, const uint16_t *refs, bool engine_refs, int nframes, const mip_pred_item *d_items,
+                          int64_t n, uint16_t *d_out, int64_t out_samples, uint32_t *d_skipped, hipStream_t s) {
+  mipgpu::PredictArgs a{};
+  a.refs = refs;
+  a.items = d_items;
+  a.n = n;
+  a.unavail = e->d_pred_unavail[engine_refs ? 1 : 0];
+  a.geo = e->d_pred_geo;
+  a.out = d_out;
+  a.out_samples = out_samples;
+  a.skipped = d_skipped;
+  a.width = e->width;
+  a.height = e->height;
+  a.ctu_cols = e->ctu_cols;
+  a.nctus = e->nctus;
+  a.nframes = nframes;
+  a.refs_vec = (reinterpret_cast<uintptr_t>(refs) & 7) == 0;
+  HIP_TRY(mipgpu::launch_predict(a, s));
+  return 0;
+}
+
+static int predict_args_ok(const mip_engine *e, int nframes, const void *items, int64_t n, const void *out,
+                           int64_t out_samples) {
+  if (nframes < 1 || n < 0 || out_samples < 0 || (n && (!items || !out))) return fail("bad prediction arguments");
+  if (n > kMaxCus) return fail("%lld prediction items exceed %lld per call", (long long)n, kMaxCus);
+  if ((long long)nframes * e->nctus * MIP_CUS_PER_CTU > kMaxCus) return fail("%d frames exceed %lld CUs per call", nframes, kMaxCus);
+  return 0;
+}
+
+int mip_predict_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes,
+                       const mip_pred_item *d_items, int64_t n, uint16_t *d_out, int64_t out_samples,
+                       uint32_t *d_skipped, void *stream) {
+  if (!e) return fail("engine is NULL");
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (!d_frames && !d_refs) return fail("bad prediction arguments: no frames");
+  if (predict_args_ok(e, nframes, d_items, n, d_out, out_samples) != 0) return -1;
+  if ((reinterpret_cast<uintptr_t>(d_out) & 7) || (reinterpret_cast<uintptr_t>(d_items) & 7))
+    return fail("d_out and d_items must be 8-byte aligned");
+  if (n == 0) return 0;
+  HIP_TRY(hipSetDevice(e->device));
+  if (flush_open(e) != 0) return -1;  // (device-API work orders itself after the host calls)
+  if (ensure_pred_tables(e) != 0) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  const uint16_t *refs = d_refs ? d_refs : d_frames;
+  const bool engine_refs = !d_refs && e->opts.filter != MIP_FILTER_NONE;
+  if (engine_refs) {  // as mip_search_device: filter into the engine's reference scratch
+    if (nframes > e->opts.max_batch) return fail("nframes %d > max_batch %d", nframes, e->opts.max_batch);
+    if (e->refs_pending) HIP_TRY(hipStreamWaitEvent(s, e->refs_done, 0));
+    if (e->host_pending)
+      HIP_TRY(hipStreamWaitEvent(s, e->call_done[(e->host_calls - 1) % mip_engine::kCallRing], 0));
+    if (mip_filter_device(d_frames, e->d_refs, e->width, e->height, nframes, e->opts.filter, e->opts.kernel_idx, s) != 0)
+      return -1;
+    refs = e->d_refs;
+  }
+  if (predict_launch(e, refs, engine_refs, nframes, d_items, n, d_out, out_samples, d_skipped, s) != 0) return -1;
+  if (engine_refs) {
+    HIP_TRY(hipEventRecord(e->refs_done, s));
+    e->refs_pending = true;
+  }
+  return 0;
+}
+
+int mip_predict_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
+                       const mip_pred_item *items, int64_t n, uint16_t *out, int64_t out_samples, int64_t *skipped) {
+  if (!e) return fail("engine is NULL");
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (!frames && !refs_or_null) return fail("bad prediction arguments: no frames");
+  if (predict_args_ok(e, nframes, items, n, out, out_samples) != 0) return -1;
+  if (out_samples && !out) return fail("bad prediction arguments: out is NULL");
+  // the list on the host: names outside the call's frames / the frame's CUs are the caller's bug
+  for (int64_t i = 0; i < n; i++) {
+    if (items[i].frame < 0 || items[i].frame >= nframes)
+      return fail("prediction item %lld: frame %d outside 0..%d", (long long)i, items[i].frame, nframes - 1);
+    if (items[i].cu < 0 || items[i].cu >= e->nctus * MIP_CUS_PER_CTU)
+      return fail("prediction item %lld: cu %d outside 0..%d", (long long)i, items[i].cu, e->nctus * MIP_CUS_PER_CTU - 1);
+  }
+  if (skipped) *skipped = 0;
+  if (out_samples == 0) {
+    if (skipped) *skipped = n;
+    return 0;
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  if (flush_open(e) != 0) return -1;
+  if (ensure_pred_tables(e) != 0) return -1;
+  if (wait_refs_readers(e) != 0) return -1;
+  // asynchronous host searches still in flight use d_frames / d_refs: let them finish
+  HIP_TRY(hipStreamSynchronize(e->stream2));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream4));
+  HIP_TRY(hipStreamSynchronize(e->stream3));
+  const size_t fs = (size_t)e->width * e->height, fbytes = fs * (size_t)nframes * 2;
+  const bool engine_refs = !refs_or_null && e->opts.filter != MIP_FILTER_NONE;
+  // the call's own device buffers (through the device block cache); the engine's frame buffers
+  // serve when the call's frames fit them
+  uint16_t *t_in = nullptr, *t_refs = nullptr, *d_out = nullptr;
+  mip_pred_item *d_items = nullptr;
+  uint32_t *d_skip = nullptr;
+  auto done = [&](int rc) {
+    for (void *p : {(void *)t_in, (void *)t_refs, (void *)d_out, (void *)d_items, (void *)d_skip}) dev_free(p);
+    return rc;
+  };
+#define PRED_TRY(expr)                                                                     \
+  do {                                                                                     \
+    hipError_t _e = (expr);                                                                \
+    if (_e != hipSuccess) return done(fail("%s: %s", #expr, hipGetErrorString(_e)));       \
+  } while (0)
+  uint16_t *d_in = e->d_frames, *d_refs = e->d_refs;
+  if (nframes > e->hp_frames) {
+    PRED_TRY(dev_malloc(e->device, (void **)&t_in, fbytes));
+    d_in = t_in;
+  }
+  if (engine_refs && (nframes > e->hp_frames || !d_refs)) {
+    PRED_TRY(dev_malloc(e->device, (void **)&t_refs, fbytes));
+    d_refs = t_refs;
+  }
+  PRED_TRY(dev_malloc(e->device, (void **)&d_out, (size_t)out_samples * 2));
+  PRED_TRY(dev_malloc(e->device, (void **)&d_items, std::max<size_t>(1, (size_t)n) * sizeof(mip_pred_item)));
+  PRED_TRY(dev_malloc(e->device, (void **)&d_skip, sizeof(uint32_t)));
+  hipStream_t s = e->stream;
+  PRED_TRY(hipMemcpyAsync(d_in, refs_or_null ? refs_or_null : frames, fbytes, hipMemcpyHostToDevice, s));
+  if (n) PRED_TRY(hipMemcpyAsync(d_items, items, (size_t)n * sizeof(mip_pred_item), hipMemcpyHostToDevice, s));
+  PRED_TRY(hipMemsetAsync(d_out, 0xff, (size_t)out_samples * 2, s));  // MIP_PRED_NONE
+  PRED_TRY(hipMemsetAsync(d_skip, 0, sizeof(uint32_t), s));
+  const uint16_t *refs = d_in;
+  if (engine_refs) {
+    // (in batches of max_batch frames like mip_filter_frames: the filter kernel's launch limit)
+    for (int f0 = 0; f0 < nframes; f0 += e->opts.max_batch) {
+      const int nb = std::min(e->opts.max_batch, nframes - f0);
+      if (mip_filter_device(d_in + f0 * fs, d_refs + f0 * fs, e->width, e->height, nb, e->opts.filter, e->opts.kernel_idx,
+                            s) != 0)
+        return done(-1);
+    }
+    refs = d_refs;
+  }
+  if (predict_launch(e, refs, engine_refs, nframes, d_items, n, d_out, out_samples, d_skip, s) != 0) return done(-1);
+  uint32_t nskip = 0;
+  PRED_TRY(hipMemcpyAsync(out, d_out, (size_t)out_samples * 2, hipMemcpyDeviceToHost, s));
+  PRED_TRY(hipMemcpyAsync(&nskip, d_skip, sizeof nskip, hipMemcpyDeviceToHost, s));
+  PRED_TRY(hipStreamSynchronize(s));
+#undef PRED_TRY
+  e->refs_pending = false;
+  if (skipped) *skipped = nskip;
+  return done(0);
 }
 
 double mip_time_search_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes,

@@ -54,6 +54,13 @@ def filter_index(name) -> int:
     return FILTERS.index(name)
 
 
+# mip_pred_item (include/mipgpu.h): one (frame, CU, mode) whose predicted samples are wanted,
+# and where they go in the output buffer.
+PRED_ITEM = np.dtype([("frame", "<i4"), ("cu", "<i4"), ("mode", "<i4"), ("pitch", "<i4"), ("offset", "<i8")])
+PRED_LAYOUTS = {"packed": 0, "frame": 1}   # MIP_PRED_PACKED / MIP_PRED_FRAME
+PRED_NONE = 0xFFFF                         # MIP_PRED_NONE: host output samples no item wrote
+
+
 class _Opts(ctypes.Structure):
     _fields_ = [("filter", ctypes.c_int), ("kernel_idx", ctypes.c_int), ("max_batch", ctypes.c_int),
                 ("want_sad_satd", ctypes.c_int), ("slices_per_ctu", ctypes.c_int), ("best_k", ctypes.c_int)]
@@ -130,6 +137,9 @@ def library():
         "mip_filter_device": (ip, [vp, vp, ip, ip, ip, ip, ip, vp]),
         "mip_copy_device": (ip, [vp, vp, ctypes.c_size_t, vp]),
         "mip_topk_device": (ip, [vp, ip, ip, ip, ip, vp, vp, vp]),
+        "mip_pred_layout": (ip, [ip, ip, ip, ip, vp, i64, ctypes.POINTER(i64)]),
+        "mip_predict_device": (ip, [vp, vp, vp, ip, vp, i64, vp, i64, vp, vp]),
+        "mip_predict_frames": (ip, [vp, vp, vp, ip, vp, i64, vp, i64, ctypes.POINTER(i64)]),
         "mip_time_search_device": (ctypes.c_double, [vp, vp, vp, ip, vp, ip]),
         "mip_host_stats": (ip, [vp, ctypes.POINTER(ctypes.c_uint64), ip]),
         "mip_host_alloc": (ip, [ctypes.c_size_t, ctypes.POINTER(vp)]),
@@ -399,6 +409,39 @@ class MipEngine:
         with self._lock:
             _check(library().mip_check_input(self._h, ctypes.c_void_p(s.cuda_stream)))
 
+    # ------------------------------------------------------- prediction output
+    def predict(self, frames, items, out_samples, refs=None):
+        """Predicted samples of the list `items` (PRED_ITEM array, see pred_items) for host
+        frames (mip_predict_frames).  Returns (uint16 array of out_samples, skipped): samples
+        no item wrote are PRED_NONE; skipped counts the items that were not written
+        (unavailable CUs, mode "none", blocks that do not fit)."""
+        f = self._frames(frames)
+        r = None if refs is None else self._frames(refs)
+        it = np.ascontiguousarray(items, dtype=PRED_ITEM)
+        out = np.empty(int(out_samples), np.uint16)
+        skipped = ctypes.c_int64()
+        with self._lock:
+            _check(library().mip_predict_frames(self._h, _ptr(f), _ptr(r), f.shape[0], _ptr(it), it.size, _ptr(out),
+                                                int(out_samples), ctypes.byref(skipped)))
+        return out, int(skipped.value)
+
+    def predict_device(self, frames, items, out, refs=None, skipped=None, stream=None):
+        """Asynchronous prediction on device tensors (mip_predict_device): `items` is a uint8
+        tensor of the PRED_ITEM bytes (torch.from_numpy(items.view(np.uint8)).cuda()), `out` a
+        uint16 / int16 tensor the blocks are written into (other samples are left as they are),
+        `skipped` an optional zeroed int32 tensor of one element that counts the items not
+        written.  Returns `out`."""
+        import torch
+        nbytes = items.numel() * items.element_size()
+        if nbytes % PRED_ITEM.itemsize:
+            raise MipError("predict_device: items is not a whole number of %d-byte entries" % PRED_ITEM.itemsize)
+        s = stream if stream is not None else torch.cuda.current_stream(frames.device)
+        with self._lock:
+            _check(library().mip_predict_device(self._h, _ptr(frames), _ptr(refs), frames.shape[0], _ptr(items),
+                                                nbytes // PRED_ITEM.itemsize, _ptr(out), out.numel(), _ptr(skipped),
+                                                ctypes.c_void_p(s.cuda_stream)))
+        return out
+
     def time_search_device(self, frames, costs, refs=None, reps=10) -> float:
         with self._lock:
             ms = library().mip_time_search_device(self._h, _ptr(frames), _ptr(refs), frames.shape[0], _ptr(costs),
@@ -433,6 +476,25 @@ def unavailable_cus(width, height, filter=None) -> np.ndarray:
     out = np.zeros(n, np.uint8)
     _check(library().mip_unavailable_cus(int(width), int(height), filter_index(filter), out.ctypes.data))
     return out.astype(bool)
+
+
+def pred_items(width, height, frame, cu, mode, layout="packed", nframes=None):
+    """Prediction list for (frame, cu, mode) triples (arrays broadcast against each other; cu
+    as in the decision lists, mode as in best_mode -- 0xff = none): returns (items, out_samples)
+    with pitch / offset filled by mip_pred_layout.  layout "packed": blocks back to back in list
+    order, row-major w x h (slice with layout.cu_geometry); "frame": blocks at their place in
+    `nframes` frame-shaped canvases (default: the largest frame index + 1)."""
+    frame, cu, mode = np.broadcast_arrays(np.asarray(frame, np.int64), np.asarray(cu, np.int64), np.asarray(mode, np.int64))
+    items = np.zeros(frame.size, PRED_ITEM)
+    items["frame"], items["cu"], items["mode"] = frame.ravel(), cu.ravel(), mode.ravel()
+    if nframes is None:
+        nframes = int(items["frame"].max()) + 1 if items.size else 1
+    if layout not in PRED_LAYOUTS:
+        raise MipError(f"unknown prediction layout {layout!r}")
+    n = ctypes.c_int64()
+    _check(library().mip_pred_layout(int(width), int(height), int(nframes), PRED_LAYOUTS[layout], _ptr(items), items.size,
+                                     ctypes.byref(n)))
+    return items, int(n.value)
 
 
 def topk_device(costs, width, height, k, modes=None, costs_k=None, stream=None):
@@ -471,6 +533,6 @@ def filter_device(frames_in, frames_out, filter, kernel_idx=0, stream=None):
     return frames_out
 
 
-__all__ = ["MipEngine", "MipError", "build_id", "source_id", "FILTERS", "FILTER_NONE", "filter_index", "filter_device", "topk_device", "library",
+__all__ = ["PRED_ITEM", "PRED_NONE", "pred_items", "MipEngine", "MipError", "build_id", "source_id", "FILTERS", "FILTER_NONE", "filter_index", "filter_device", "topk_device", "library",
            "pinned_empty", "unavailable_cus", "numa_node", "bind_thread", "device_cache", "copy_device",
            "layout", "SHAPES", "COSTS_PER_CTU", "CUS_PER_CTU", "UNAVAILABLE", "num_ctus"]

@@ -138,6 +138,35 @@ def expand_cu_mask(cu_mask: np.ndarray, nctus: int) -> np.ndarray:
     return m[:, _entry_cu()].reshape(-1)
 
 
+@lru_cache(maxsize=None)
+def _ctu_cus():
+    """Shape index and CTU-relative position of the 5380 CUs of one CTU, CU order."""
+    shape = np.concatenate([np.full(s.ncu, s.index, np.int32) for s in SHAPES])
+    pos = [s.positions() for s in SHAPES]
+    x = np.concatenate([p[0] for p in pos]).astype(np.int32)
+    y = np.concatenate([p[1] for p in pos]).astype(np.int32)
+    for a in (shape, x, y):
+        a.setflags(write=False)
+    return shape, x, y
+
+
+def cu_geometry(width: int, height: int, cu):
+    """Geometry of CUs named by their index in a frame's decision lists (ctu*5380 + shape CU
+    prefix + cu; vectorised): returns shape, x, y, w, h -- the shape index, the frame position
+    of the top-left sample and the block size.  Callers of the prediction output need w * h to
+    slice a packed buffer and (x, y) to place a block."""
+    cu = np.asarray(cu, np.int64)
+    if cu.size and (cu.min() < 0 or cu.max() >= num_ctus(width, height) * CUS_PER_CTU):
+        raise ValueError("cu index outside the frame's CUs")
+    cols, _ = ctu_grid(width, height)
+    shape, lx, ly = _ctu_cus()
+    ctu, k = cu // CUS_PER_CTU, cu % CUS_PER_CTU
+    sh = shape[k]
+    ws = np.array([s.w for s in SHAPES], np.int32)
+    hs = np.array([s.h for s in SHAPES], np.int32)
+    return sh, (128 * (ctu % cols) + lx[k]).astype(np.int32), (128 * (ctu // cols) + ly[k]).astype(np.int32), ws[sh], hs[sh]
+
+
 def cu_count(nctus: int) -> int:
     return nctus * CUS_PER_CTU
 
