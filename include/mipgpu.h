@@ -311,6 +311,26 @@ int mip_pop_times(mip_engine *e, double *upload_ms, double *filter_ms, int max, 
  * chunks, out[3] merged launches (n entries of out are written, n <= 4). */
 int mip_host_stats(mip_engine *e, uint64_t *out, int n);
 
+/* Search-launch census of the engine (diagnostics, tests; additive to ABI 7): which instance
+ * of the search kernel every search launch of the engine ran -- host pipeline chunks, device-API
+ * searches and mip_time_search_device alike -- counted since the engine was created.
+ *   out[8*w + 4*alt + 2*dec + pf]  launches of the instance with
+ *       w    0: 12-wave workgroups, 1: 16-wave ("wide", small launches), 2: 8-wave (the
+ *            four-wave twin of the host pipeline),
+ *       alt  1: alternative (filtered or caller-supplied) references,
+ *       dec  1: decisions only (no cost table),
+ *       pf   1: the instance that prefetches the next item's window (as launched, not as asked);
+ *   out[MIP_CENSUS_PAIR]     launches in pair mode (16-wave workgroups taking two items at once),
+ *   out[MIP_CENSUS_CHUNKED]  launches whose item queue was cut into per-XCD chunks,
+ *   out[MIP_CENSUS_ORDERED]  launches that took their items longest first (else raster order).
+ * n entries of out are written, n <= MIP_CENSUS_ENTRIES.  Launches that failed are not counted. */
+#define MIP_CENSUS_INSTANCES 24
+#define MIP_CENSUS_PAIR 24
+#define MIP_CENSUS_CHUNKED 25
+#define MIP_CENSUS_ORDERED 26
+#define MIP_CENSUS_ENTRIES 27
+int mip_search_census(mip_engine *e, uint64_t *out, int n);
+
 /* Page-locked host memory (hipHostMalloc): host buffers for mip_search_frames /
  * mip_filter_frames allocated here are transferred by DMA at full PCIe rate (pageable
  * buffers are staged through the runtime -- the cost table is 52.8 MB per 1080p frame).

@@ -38,6 +38,15 @@ def test_small_configs_vs_oracle_and_reference(gpu_available, name):
     with _engine(c, want_sad_satd=True) as eng:
         out = eng.search(frames, sad_satd=True)
         filt = eng.filter_frames(frames, c["filter"], c["kernel_idx"]) if c["filter"] else None
+    _assert_small_config(fx, frames, out, filt)
+
+
+def _assert_small_config(fx, frames, out, filt):
+    """A reference-made small fixture against the engine's tables `out` and filtered frames
+    `filt` (None without a filter): the oracle on every entry, the UNAVAILABLE set, the
+    reference's hashes of the defined entries and -- when `out` holds decisions -- the argmin
+    of the table."""
+    c = fx["config"]
     for f, fr in enumerate(fx["frames"]):
         refs, und, mask = G.refs_and_mask(fx, frames, f)
         oc, osad, osatd = O.engine_search(frames[f], c["filter"], c["kernel_idx"], want_sad_satd=True)
@@ -57,6 +66,40 @@ def test_small_configs_vs_oracle_and_reference(gpu_available, name):
         if filt is not None:
             assert np.array_equal(filt[f], refs)
             assert G.filtered_sha(filt[f], und) == fr["filtered_sha256"]
+        if "best_mode" in out:
+            bm, bc = layout.best_modes(oc, layout.num_ctus(c["width"], c["height"]))
+            assert np.array_equal(out["best_mode"][f], bm)
+            assert np.array_equal(out["best_cost"][f], bc)
+
+
+def _waves(census):
+    """Waves per workgroup of the search launches a census (or a census difference) counts."""
+    return {k[0] for k, v in census.items() if isinstance(k, tuple) and v}
+
+
+def _census_delta(before, after):
+    return {k: after[k] - before[k] for k in after}
+
+
+@pytest.mark.parametrize("waves,pk", [(12, "0"), (8, "8")])
+@pytest.mark.parametrize("name", [n for n in SMALL if n.startswith("w416_")])
+def test_w416_configs_through_the_batched_kernels(gpu_available, monkeypatch, name, waves, pk):
+    """The reference-made 416x240 fixtures (every filter family and original references) are
+    small launches, which the 16-wave kernel serves by default
+    (test_small_configs_vs_oracle_and_reference).  Here they go through the 12-wave kernel
+    (MIPGPU_WIDE=0, MIPGPU_PIPE_KERNEL=0) and through the four-wave twin (MIPGPU_PIPE_KERNEL=8)
+    -- the census proves it -- under the same assertions, plus the decisions."""
+    monkeypatch.setenv("MIPGPU_WIDE", "0")
+    monkeypatch.setenv("MIPGPU_PIPE_KERNEL", pk)
+    fx = G.load(name)
+    c = fx["config"]
+    frames = G.inputs(fx)
+    with _engine(c, want_sad_satd=True) as eng:
+        out = eng.search(frames, sad_satd=True, best=True)
+        census = eng.search_census()
+        filt = eng.filter_frames(frames, c["filter"], c["kernel_idx"]) if c["filter"] else None
+    assert _waves(census) == {waves}, census
+    _assert_small_config(fx, frames, out, filt)
 
 
 @pytest.mark.parametrize("name", [n for n in G.names() if n not in SMALL])
@@ -624,13 +667,25 @@ def test_prefetching_launch_equals_small_launches(gpu_available):
     W, H, n = 1920, 1080, 34
     frames = torch.from_numpy(synth_frames(W, H, n, 0x9F0, 0).astype(np.int16)).cuda()
     with MipEngine(W, H, max_batch=n) as eng:
+        c0 = eng.search_census()
         big = eng.search_device(frames)
+        c1 = eng.search_census()
         small = torch.empty_like(big)
         for f in range(0, n, 2):
             eng.search_device(frames[f:f + 2], costs=small[f:f + 2])
+        c2 = eng.search_census()
         bm = torch.full((n, eng.cus_per_frame), 0x5a, dtype=torch.uint8, device="cuda")
         bc = torch.full((n, eng.cus_per_frame), -5, dtype=torch.int32, device="cuda")
         eng.search_device(frames, costs=False, best_mode=bm, best_cost=bc)
+        c3 = eng.search_census()
+        # the census: the big launches ran the prefetching instances on a chunked queue, the
+        # two-frame ones the plain 12-wave instance
+        for d, want, chunked in ((_census_delta(c0, c1), {(12, 0, 0, 1): 1}, 1),
+                                 (_census_delta(c1, c2), {(12, 0, 0, 0): n // 2}, 0),
+                                 (_census_delta(c2, c3), {(12, 0, 1, 1): 1}, 1)):
+            print("census", {k: v for k, v in d.items() if v})
+            assert {k: v for k, v in d.items() if isinstance(k, tuple) and v} == want
+            assert d["chunked"] == chunked
         tm, tc = topk_device(big, W, H, 1)
         torch.cuda.synchronize()
         assert torch.equal(big, small)
@@ -675,7 +730,10 @@ def test_small_launch_shapes_agree(gpu_available, monkeypatch, w, h, n, filt, k)
     order (MIPGPU_ORDER).  The knobs are read per launch (mipgpu.cpp wide_launch,
     lpt_order_enabled, the pair knob): one engine runs every combination, and every
     combination must give the same cost / SAD / SATD tables and decisions (full table and
-    fused decisions-only), equal to the oracle's."""
+    fused decisions-only), equal to the oracle's.  The census says what each round ran
+    (DESIGN.md section 5.1): 16 waves only with MIPGPU_WIDE=1 and the longest-first order --
+    MIPGPU_ORDER=0 takes the large-launch work lists whatever MIPGPU_WIDE says -- and, through
+    the host API used here, the four-wave twin otherwise."""
     frames = synth_frames(w, h, n, 0x5A11 + w, 1)
     outs = []
     with MipEngine(w, h, max_batch=n, filter=filt, kernel_idx=k, want_sad_satd=True) as eng:
@@ -684,9 +742,22 @@ def test_small_launch_shapes_agree(gpu_available, monkeypatch, w, h, n, filt, k)
             monkeypatch.setenv("MIPGPU_WIDE", wide)
             monkeypatch.setenv("MIPGPU_PAIR", pair)
             monkeypatch.setenv("MIPGPU_ORDER", order)
+            c0 = eng.search_census()
             full = eng.search(frames, best=True, sad_satd=True)
             dec = eng.search(frames, costs=False, best=True)
+            d = _census_delta(c0, eng.search_census())
+            print("census", (wide, pair, order), {k: v for k, v in d.items() if v})
             outs.append(((wide, pair, order), full, dec))
+            # what ran: MIPGPU_WIDE=1 with the longest-first order gives 16-wave workgroups, in
+            # pair mode exactly with original references and MIPGPU_PAIR on; MIPGPU_ORDER=0
+            # takes the large-launch work lists (mipgpu.cpp pick_work), i.e. never 16 waves
+            launches = sum(v for k, v in d.items() if isinstance(k, tuple))
+            if wide == "1" and order == "1":
+                assert _waves(d) == {16}, (wide, pair, order, d)
+                assert d["pair"] == (launches if filt is None and pair == "1" else 0), (wide, pair, order, d)
+            else:
+                assert 16 not in _waves(d) and d["pair"] == 0, (wide, pair, order, d)
+            assert d["ordered"] == (launches if order == "1" else 0), (wide, pair, order, d)
     ref = outs[0][1]
     for knobs, full, dec in outs:
         for key in ("cost", "sad", "satd", "best_mode", "best_cost"):
@@ -819,6 +890,9 @@ def test_merged_launches_keep_each_call_its_own(gpu_available, monkeypatch, filt
     monkeypatch.setenv("MIPGPU_MERGE", "hold")
     monkeypatch.setenv("MIPGPU_PIPE_KERNEL", pk)
     monkeypatch.setenv("MIPGPU_GATHER_DOWN", gather)  # merged decisions-only downloads: one copy kernel / per member
+    # (at this size every chunk is below the 16-wave threshold, and 16-wave launches ignore
+    # MIPGPU_PIPE_KERNEL: without this the census shows (16, ...) instances only, whatever pk)
+    monkeypatch.setenv("MIPGPU_WIDE", "0")
     w, h = 264, 136
     n = 23
     frames = synth_frames(w, h, n, 0x3E6 + (k or 0), 0)
@@ -856,6 +930,9 @@ def test_merged_launches_keep_each_call_its_own(gpu_available, monkeypatch, filt
             except MipError as exc:
                 results.append(exc)
         stats = eng.host_stats()
+        census = eng.search_census()
+    print("census", pk, {k: v for k, v in census.items() if v})
+    assert _waves(census) == ({8} if pk == "4" else {12}), (pk, census)
     assert stats["merged_launches"] == 4 and stats["merged_calls"] == 13, stats
     assert stats["calls"] == len(calls) and stats["launches"] >= 5, stats
     for (f0, nf, kind), res in zip(calls, results):
@@ -891,6 +968,9 @@ def test_merged_launches_1080p_default_policy(gpu_available, monkeypatch):
     monkeypatch.setenv("MIPGPU_PIPE_KERNEL", "0")
     with MipEngine(W, H, max_batch=4) as ref_eng:
         want = ref_eng.search(pool, best=True)
+        ref_census = ref_eng.search_census()
+    print("census ref", {k: v for k, v in ref_census.items() if v})
+    assert _waves(ref_census) == {12}, ref_census
     monkeypatch.delenv("MIPGPU_PIPE_KERNEL")
     with MipEngine(W, H, max_batch=8) as eng:
         pf = pinned_empty(pool.shape, np.uint16)
@@ -934,6 +1014,9 @@ def test_merged_launches_1080p_default_policy(gpu_available, monkeypatch):
         o4, o1, o2 = eng.wait(t4), eng.wait(t1), eng.wait(t2)
         assert np.array_equal(o4["best_cost"], want["best_cost"])
         assert np.array_equal(o1["best_mode"][0], want["best_mode"][1]) and np.array_equal(o2["best_mode"][0], want["best_mode"][3])
+        census = eng.search_census()
+    print("census", {k: v for k, v in census.items() if v})
+    assert 8 in _waves(census), census  # the queued calls did meet the four-wave twin
 
 
 def test_engine_churn_reuses_parked_device_blocks(gpu_available):

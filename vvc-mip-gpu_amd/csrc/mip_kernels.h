@@ -204,13 +204,26 @@ int search_resident_groups(bool alt_refs, bool wide);
 #if !defined(MIP_FOUR_WAVE_TWIN) || !MIP_FOUR_WAVE_TWIN  // (in the twin the names above are these)
 int search_resident_groups_four(bool alt_refs, bool wide);
 #endif
+// What a launch_search call launched (diagnostics: mip_search_census): the kernel instance
+// mip_search_kernel<alt, dec, pf, waves> and its launch modes after launch_search's own
+// filtering of the arguments.
+struct SearchLaunchInfo {
+  int waves;     // per workgroup: 12, 16 or 8
+  bool alt;      // alternative references
+  bool dec;      // decisions only
+  bool pf;       // the prefetching instance
+  bool pair;     // pair mode (SearchArgs::nonempty > 0)
+  bool chunked;  // more than one queue chunk
+  bool ordered;  // longest-first item order (SearchArgs::order)
+};
 // done: optional event recorded by the kernel's own dispatch (hipExtLaunchKernel's stop
-// event) instead of a separate marker packet behind it.
+// event) instead of a separate marker packet behind it.  info: optional, filled for every
+// launch that was attempted.
 hipError_t launch_search(const SearchArgs &a, int nframes, bool alt_refs, int resident, bool wide, hipStream_t s,
-                         hipEvent_t done = nullptr);
+                         hipEvent_t done = nullptr, SearchLaunchInfo *info = nullptr);
 #if !defined(MIP_FOUR_WAVE_TWIN) || !MIP_FOUR_WAVE_TWIN
 hipError_t launch_search_four(const SearchArgs &a, int nframes, bool alt_refs, int resident, bool wide, hipStream_t s,
-                         hipEvent_t done = nullptr);
+                         hipEvent_t done = nullptr, SearchLaunchInfo *info = nullptr);
 #endif
 hipError_t launch_best_modes(const BestArgs &a, hipStream_t s);
 // Decisions only, CUs whose mode pairs are cut over several tasks (split CUs of the CTU's

@@ -2226,7 +2226,7 @@ int search_resident_groups(bool alt, bool wide) {
 }
 
 hipError_t launch_search(const SearchArgs &args, int nframes, bool alt_refs, int resident, bool wide, hipStream_t s,
-                         hipEvent_t done) {
+                         hipEvent_t done, SearchLaunchInfo *info) {
   if (args.slices < 1 || !args.queue || !args.status || resident < 1) return hipErrorInvalidValue;
   SearchArgs a = args;
   if (a.ctu0 < 0 || a.nrange < 1 || a.ctu0 + a.nrange > a.nctus) return hipErrorInvalidValue;
@@ -2249,6 +2249,9 @@ hipError_t launch_search(const SearchArgs &args, int nframes, bool alt_refs, int
   if (dec && (!a.best_cost || !a.dfill_begin)) return hipErrorInvalidValue;
   const bool pf = kPrefetchKernel && !alt_refs && !wide && a.nitems >= (uint32_t)MIP_PREFETCH_MIN_ITEMS * (uint32_t)groups;
   const size_t lds = search_lds_bytes(alt_refs, pf, wide ? kWideWaves : kSearchWaves);
+  if (info)  // (the instance chosen below, and the launch modes the kernel sees)
+    *info = SearchLaunchInfo{wide ? kWideWaves : kSearchWaves, alt_refs, dec, pf, a.nonempty > 0, a.chunks > 1,
+                             a.order != nullptr};
   const dim3 grid(groups);
   constexpr int S = kSearchWaves, L = kWideWaves;
   (void)L;

@@ -693,6 +693,7 @@ struct mip_engine {
   int last_slot = -1;  // slot of the last launched host-pipeline chunk (its slot_comp event)
   int last_frames = 0;  // frames of the last launched host-pipeline chunk (merge_cap)
   uint64_t stat_launches = 0, stat_merged_calls = 0, stat_merged_launches = 0;  // mip_host_stats
+  uint64_t census[MIP_CENSUS_ENTRIES] = {};  // mip_search_census (search_device_impl)
   // per-frame status pointers of merged launches ([kCallRing][hp_cap], page-locked, mapped;
   // row (first call - 1) % kCallRing), SearchArgs::frame_status
   uint32_t **h_frame_status = nullptr, **d_frame_status = nullptr;
@@ -1498,9 +1499,17 @@ static int search_device_impl(mip_engine *e, const uint16_t *d_frames, const uin
   const bool last = !(alt && e->nfixup[map]) && !engine_refs && !timing &&
                     (decisions_only ? defer_split != nullptr : !(d_best || d_best_cost)) && ext_done_enabled();
   hipEvent_t stop = done && last ? *done : nullptr;
-  const hipError_t le = four ? SLOW_CALL(mipgpu::launch_search_four(a, nframes, alt, resident, false, s, stop))
-                             : SLOW_CALL(mipgpu::launch_search(a, nframes, alt, resident, work.wide, s, stop));
+  mipgpu::SearchLaunchInfo li{};
+  const hipError_t le = four ? SLOW_CALL(mipgpu::launch_search_four(a, nframes, alt, resident, false, s, stop, &li))
+                             : SLOW_CALL(mipgpu::launch_search(a, nframes, alt, resident, work.wide, s, stop, &li));
   if (le == hipSuccess && stop) *done = nullptr;
+  if (le == hipSuccess) {  // mip_search_census (every caller holds e->mu)
+    const int w = li.waves == 12 ? 0 : li.waves == 16 ? 1 : 2;
+    e->census[8 * w + 4 * li.alt + 2 * li.dec + li.pf]++;
+    e->census[MIP_CENSUS_PAIR] += li.pair;
+    e->census[MIP_CENSUS_CHUNKED] += li.chunked;
+    e->census[MIP_CENSUS_ORDERED] += li.ordered;
+  }
   if (le != hipSuccess) {
     ring.failed(slot);  // the pair is cleared before its next use
     return fail("search launch failed: %s", hipGetErrorString(le));
@@ -2165,6 +2174,13 @@ int mip_host_stats(mip_engine *e, uint64_t *out, int n) {
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   const uint64_t v[4] = {e->host_calls, e->stat_launches, e->stat_merged_calls, e->stat_merged_launches};
   for (int i = 0; i < n; i++) out[i] = v[i];
+  return 0;
+}
+
+int mip_search_census(mip_engine *e, uint64_t *out, int n) {
+  if (!e || !out || n < 0 || n > MIP_CENSUS_ENTRIES) return fail("bad arguments");
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  for (int i = 0; i < n; i++) out[i] = e->census[i];
   return 0;
 }
 

@@ -142,6 +142,7 @@ def library():
         "mip_predict_frames": (ip, [vp, vp, vp, ip, vp, i64, vp, i64, ctypes.POINTER(i64)]),
         "mip_time_search_device": (ctypes.c_double, [vp, vp, vp, ip, vp, ip]),
         "mip_host_stats": (ip, [vp, ctypes.POINTER(ctypes.c_uint64), ip]),
+        "mip_search_census": (ip, [vp, ctypes.POINTER(ctypes.c_uint64), ip]),
         "mip_host_alloc": (ip, [ctypes.c_size_t, ctypes.POINTER(vp)]),
         "mip_host_free": (ip, [vp]),
         "mip_host_alloc_near": (ip, [ip, ctypes.c_size_t, ctypes.POINTER(vp)]),
@@ -356,6 +357,20 @@ class MipEngine:
         with self._lock:
             _check(library().mip_host_stats(self._h, out, 4))
         return dict(zip(("calls", "launches", "merged_calls", "merged_launches"), (int(v) for v in out)))
+
+    def search_census(self) -> dict:
+        """Search launches of the engine so far by kernel instance (mip_search_census): keys
+        (waves per workgroup, alt, dec, pf) -- 12, 16 or 8 waves; alternative references;
+        decisions only; the prefetching instance -- for all 24 combinations, plus the launch
+        counts 'pair' (pair mode), 'chunked' (per-XCD queue chunks) and 'ordered' (items
+        longest first)."""
+        out = (ctypes.c_uint64 * 27)()
+        with self._lock:
+            _check(library().mip_search_census(self._h, out, 27))
+        res = {(w, a, d, p): int(out[8 * i + 4 * a + 2 * d + p])
+               for i, w in enumerate((12, 16, 8)) for a in (0, 1) for d in (0, 1) for p in (0, 1)}
+        res.update(pair=int(out[24]), chunked=int(out[25]), ordered=int(out[26]))
+        return res
 
     def flush(self):
         """Launch the engine's open (merged) chunk now (mip_flush): queued small calls are
