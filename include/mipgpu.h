@@ -340,7 +340,7 @@ int mip_host_free(void *p);
 
 /* NUMA placement (ABI 7).  Each GPU hangs off one socket of a multi-socket host; an engine
  * keeps its page-locked buffers on that GPU's NUMA node and runs its host threads (bounce-ring
- * copies, completion, merge flusher) on the node's CPUs.  mip_host_alloc_near allocates the
+ * copies, completion) on the node's CPUs.  mip_host_alloc_near allocates the
  * caller's page-locked buffers on `device`'s node (else as mip_host_alloc);
  * mip_bind_thread runs the calling thread on the node's CPUs (1 bound, 0 nothing to do: one
  * node or unknown); mip_numa_node gives the node (-1 unknown / one node);

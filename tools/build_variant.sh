@@ -15,9 +15,10 @@ tmp=$(mktemp -d)
 trap 'rm -rf "$tmp"' EXIT
 id="$(make -s KNOBS="$*" build-id)"
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -I../include -Icsrc $*"
+srcs="$(make -s hip-sources)"  # the Makefile's list: a kernel file added there is built here too
 pids=()
-for s in mip_search mip_filter mip_fixup; do
-  /opt/rocm/bin/hipcc $F -c -o "$tmp/$s.o" "csrc/$s.hip" & pids+=($!)
+for src in $srcs; do
+  /opt/rocm/bin/hipcc $F -c -o "$tmp/$(basename "$src" .hip).o" "$src" & pids+=($!)
 done
 /opt/rocm/bin/hipcc $F -DMIP_SIX_WAVES=0 -DMIP_FOUR_WAVE_TWIN=1 -c -o "$tmp/mip_search_four.o" csrc/mip_search.hip \
   2> >(grep -v "macro redefined\|^ *[0-9]* | \|^ *| \|note: previous definition\|warning generated\|^<command line>" >&2) & pids+=($!)

@@ -1,6 +1,6 @@
 // mip_kernels.h -- launch interface between the C-ABI host code (mipgpu.cpp) and the
-// gfx950 kernels (mip_search.hip, mip_filter.hip, mip_fixup.hip, mip_predict.hip).  Not part
-// of the public ABI.
+// gfx950 kernels (mip_search.hip, mip_decide.hip, mip_filter.hip, mip_fixup.hip,
+// mip_predict.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -48,14 +48,15 @@ constexpr int kClassH[kNumClasses] = {64, 32, 16, 32, 8, 32, 16, 8, 16, 4, 32, 4
 //     -- with the MIP tables and the next item's window in LDS beside a 768-word per-wave
 //     scratch: 16x16 / 16x8 and the 64-slot 4x4 / 4x8 tasks produce their reduced predictions
 //     in halves, 8xH tasks in quarters (mip_search.hip Geo, phase_a_half, walk_pairs_chunked).
-//   0: 8-wave workgroups, two per CU, four waves per SIMD, 1280-word scratch (rounds 1-5).
-//   1, 2 (round 5 experiments): 12-wave workgroups with the tables in global memory, 1152-word
-//     scratch, no prefetch / three 8-wave workgroups.
+//   0: 8-wave workgroups, two per CU, four waves per SIMD, 1280-word scratch (rounds 1-5): the
+//     four-wave twin, or a whole four-wave library as an A/B baseline.
 #ifndef MIP_SIX_WAVES
 #define MIP_SIX_WAVES 3
 #endif
-constexpr int kV16 = MIP_SIX_WAVES == 1 || MIP_SIX_WAVES == 2 ? 2 : 1;  // row parts of the 16x16 / 16x8 base classes
-constexpr int kClassV[kNumClasses] = {4, 2, 1, 2, 1, 1, kV16, kV16, 1, 1, 2, 1, 2, 1, 1, 1, 1, 2, 4, 2, 4,
+#if MIP_SIX_WAVES != 3 && MIP_SIX_WAVES != 0
+#error "MIP_SIX_WAVES must be 3 (12-wave workgroups, the default) or 0 (the four-wave design)"
+#endif
+constexpr int kClassV[kNumClasses] = {4, 2, 1, 2, 1, 1, 1, 1, 1, 1, 2, 1, 2, 1, 1, 1, 1, 2, 4, 2, 4,
                                       2, 2, 1, 1, 1, 4, 2, 4};
 constexpr bool kClassTR[kNumClasses] = {false, false, false, false, false, false, false, false, false, false, false,
                                         false, false, false, false, false, false, false, false, false, false,
@@ -192,9 +193,15 @@ struct FilterArgs {
 };
 
 // Waves per search workgroup: two 12-wave workgroups share a CU in batched launches (MIP_SIX_WAVES
-// 3; 8-wave ones with MIP_SIX_WAVES 0, three per CU with 2); small launches can run one 16-wave
-// workgroup per CU instead ("wide"), whose waves share one item's tasks (launch_search).
-constexpr int kSearchWaves = MIP_SIX_WAVES == 1 || MIP_SIX_WAVES == 3 ? 12 : 8, kWideWaves = 16;
+// 3; 8-wave ones with MIP_SIX_WAVES 0); small launches can run one 16-wave workgroup per CU
+// instead ("wide"), whose waves share one item's tasks (launch_search).
+constexpr int kSearchWaves = MIP_SIX_WAVES == 3 ? 12 : 8, kWideWaves = 16;
+// Items per workgroup from which a launch is "large": it prefetches the next item's window and
+// cuts the item queue into XCD chunks (launch_search); below it the host orders the items
+// longest first and picks the slice count (mipgpu.cpp pick_work), and alternating pipeline
+// chunks run the four-wave twin (pipe_small).  One constant, so the host and the launcher
+// never disagree about which launches are small.
+constexpr int kPrefetchMinItems = 32;
 // Workgroups of the search kernel resident on the current device at once (persistent grid
 // size); computed once per engine (mip_engine_create), 0 on error.
 int search_resident_groups(bool alt_refs, bool wide);

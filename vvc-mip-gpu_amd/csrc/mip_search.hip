@@ -40,15 +40,13 @@
 // The four-wave twin (round 6): this file compiled a second time with -DMIP_SIX_WAVES=0
 // -DMIP_FOUR_WAVE_TWIN=1 (Makefile: build/mip_search_four.o) exports the 8-wave search as
 // launch_search_four / search_resident_groups_four, which the host pipeline uses for its small
-// alternating chunks (mipgpu.cpp search_device_impl).  The helper kernels live in the
-// primary compilation only.
+// alternating chunks (mipgpu.cpp search_device_impl).
 #ifndef MIP_FOUR_WAVE_TWIN
 #define MIP_FOUR_WAVE_TWIN 0
 #endif
 #if MIP_FOUR_WAVE_TWIN
 #define launch_search launch_search_four
 #define search_resident_groups search_resident_groups_four
-#define search_lds_bytes search_lds_bytes_four
 #endif
 
 #include "mip_kernels.h"
@@ -63,50 +61,8 @@ typedef _Float16 __attribute__((ext_vector_type(2))) h2;
 typedef _Float16 __attribute__((ext_vector_type(4))) h4;
 typedef float __attribute__((ext_vector_type(4))) f4;
 
-[[maybe_unused]] __constant__ mip_shape_desc c_shapes[MIP_NUM_SHAPES] = MIP_SHAPE_TABLE;  // (helper kernels)
-// first CU (reference order inside a CTU) of every shape, for the decision-list kernel
-struct ShapeStarts {
-  uint16_t v[MIP_NUM_SHAPES + 1];
-};
-constexpr mip_shape_desc kShapesC[MIP_NUM_SHAPES] = MIP_SHAPE_TABLE;
-constexpr ShapeStarts make_shape_starts() {
-  ShapeStarts st{};
-  for (int i = 0; i < MIP_NUM_SHAPES; i++) st.v[i + 1] = (uint16_t)(st.v[i] + kShapesC[i].ncu);
-  return st;
-}
-static_assert(make_shape_starts().v[MIP_NUM_SHAPES] == MIP_CUS_PER_CTU, "shape table");
-[[maybe_unused]] __constant__ ShapeStarts c_shape_start = make_shape_starts();
-
-#ifndef MIP_PREFETCH_MIN_ITEMS
-#define MIP_PREFETCH_MIN_ITEMS 32  // items per workgroup from which a launch prefetches (A/B knob)
-#endif
-#ifndef MIP_PF_BATCH
-#define MIP_PF_BATCH 10  // window loads in flight per lane in the prefetching wave (6: -0.3 %)
-#endif
-#ifndef MIP_PHASEA_BATCH_NCS
-#define MIP_PHASEA_BATCH_NCS 2  // column sets from which phase A reads its B operands up front (A/B knob)
-#endif
-#ifndef MIP_ACC_PAIR
-#define MIP_ACC_PAIR 1  // blocks accumulated in pairs before unpacking (A/B knob)
-#endif
-#ifndef MIP_UV2_UNROLL
-#define MIP_UV2_UNROLL 2  // blocks per loop iteration, UV = 2 classes with H > 8 (A/B knob)
-#endif
-#ifndef MIP_WIN_UNROLL
-#define MIP_WIN_UNROLL 2  // windows of the vertical pass per loop iteration (A/B knob)
-#endif
-#ifndef MIP_PAIR_BLOCKS
-#define MIP_PAIR_BLOCKS 1  // classes with an even block count per lane walk block pairs (A/B knob)
-#endif
-#ifndef MIP_PRIO_BALANCE
-#define MIP_PRIO_BALANCE 0  // wave priority follows the item's remaining tasks (A/B knob; measured
-                            // -1.7 % at 384 frames / -1.5 % at 32, 1 frame 0.184 -> 0.177 ms: off)
-#endif
 #ifndef MIP_ONLY_CLASS
 #define MIP_ONLY_CLASS -1  // resource census of one size class (tools/vgpr_census.sh)
-#endif
-#ifndef MIP_SKIP_CLASSES
-#define MIP_SKIP_CLASSES 0  // bit mask of size classes compiled out (occupancy experiments; wrong tables)
 #endif
 
 constexpr int kPitch = 68;       // LDS row pitch in samples (34 dwords: conflict-free rows)
@@ -119,17 +75,13 @@ constexpr int kLatElems = (16 * kLatRowPitch + 16 * kLatColPitch + 7) / 8 * 8;
 // Wave-private LDS: per-CU MFMA inputs + reduced-prediction scratch.
 constexpr int kEntryBytes = 16;                         // 8 f16 MFMA inputs per CU
 constexpr int kCuTableBytes = 64 * kEntryBytes;
-#ifndef MIP_SCRATCH_WORDS
-// 1152 with six waves per SIMD: two 12-wave workgroups per CU in 160 KB of LDS
-// (MIP_SIX_WAVES 3, round 6: 768, the MIP tables kept in LDS, the 64-slot 4xN and the 8xH
-// tasks' reduced predictions produced in chunks of two rows, see Geo)
-#define MIP_SCRATCH_WORDS \
-  (MIP_SIX_WAVES == 1 ? 1152 : (MIP_SIX_WAVES == 2 ? 1144 : (MIP_SIX_WAVES == 3 ? 768 : 1280)))
-#endif
 // Chunks that end inside a CU's block pair or 4x4 block (MIP_SIX_WAVES 3): phase A of the next
 // chunk runs in the middle of the lane's walk (walk_pairs_chunked, walk_4x4_chunked).
 constexpr bool kSpanChunks = MIP_SIX_WAVES == 3;
-constexpr int kScratchWords = MIP_SCRATCH_WORDS;        // [slot][position] packed mode pairs
+// [slot][position] packed mode pairs.  768 with six waves per SIMD: two 12-wave workgroups per
+// CU in 160 KB of LDS beside the MIP tables, the 64-slot 4xN and the 8xH tasks' reduced
+// predictions produced in chunks of two rows (see Geo); 1280 at four waves per SIMD.
+constexpr int kScratchWords = MIP_SIX_WAVES == 3 ? 768 : 1280;
 constexpr int kWaveBytes = kCuTableBytes + kScratchWords * 4;
 constexpr int kWaveStride = kWaveBytes;  // LDS bytes between waves' private areas
 constexpr int kZeroBytes = 7 * 8 * kEntryBytes + 16;    // > every uniform B offset + 8 B
@@ -520,7 +472,6 @@ __device__ __forceinline__ uint32_t pair_finish(const uint32_t (&t)[16], uint32_
 // Packed block results -> 32-bit per-mode accumulators.
 struct Acc {
   uint32_t sad0 = 0, sad1 = 0, satd0 = 0, satd1 = 0;
-#if MIP_ACC_PAIR
   // blocks are added in pairs: two blocks' packed sums still fit 16 bits per mode
   // (SAD <= 32736, SATD <= 65472), so a pair costs two adds + the four unpacking dot2
   u2 ps{0, 0}, pt{0, 0};
@@ -540,15 +491,6 @@ struct Acc {
     if (have) unpack(ps, pt);
     have = false;
   }
-#else
-  __device__ __forceinline__ void add(u2 sad, u2 satd) {
-    sad0 = __builtin_amdgcn_udot2(sad, (u2){1, 0}, sad0, false);
-    sad1 = __builtin_amdgcn_udot2(sad, (u2){0, 1}, sad1, false);
-    satd0 = __builtin_amdgcn_udot2(satd, (u2){1, 0}, satd0, false);
-    satd1 = __builtin_amdgcn_udot2(satd, (u2){0, 1}, satd1, false);
-  }
-  __device__ __forceinline__ void flush() {}
-#endif
 };
 
 // Both modes' sums in the two 16-bit halves of one register, for CUs of at most two 4x4
@@ -805,10 +747,9 @@ __device__ __forceinline__ void walk_strip(const ORIG &orig, const RED &red, int
   } else if constexpr (G::UV == 2) {
     // Vertical pass (intra.cl:867-893) with two windows per 4x4 block: the row between
     // anchors k-1 and k is (prev + next + 1) >> 1.
-    constexpr int kUnroll = H <= 8 ? 2 : MIP_UV2_UNROLL;
     constexpr int NBLK = (G::CHUNKED ? 4 : G::KV) / 2;  // blocks in [k0, k1)
     (void)k1;
-#pragma unroll kUnroll
+#pragma unroll 2  // blocks per loop iteration
     for (int bi = 0; bi < NBLK; bi++) {
       const int by = k0 / 2 + bi;
       typename ORIG::Block b;
@@ -836,7 +777,7 @@ __device__ __forceinline__ void walk_strip(const ORIG &orig, const RED &red, int
     constexpr int NB = G::UV / 4;  // blocks per window
     constexpr int NW = G::CHUNKED ? 4 : G::KV;  // windows in [k0, k1)
     (void)k1;
-#pragma unroll MIP_WIN_UNROLL
+#pragma unroll 2  // windows per loop iteration
     for (int kk = 0; kk < NW; kk++) {
       const int k = k0 + kk;
       s2 next[4];
@@ -876,11 +817,9 @@ __device__ __forceinline__ void walk_strip(const ORIG &orig, const RED &red, int
 
 // Paired walk (see PairAcc): the lane's blocks in [k0, k0 + windows) two at a time, rows
 // generated exactly as in walk_strip; block A's residual rows wait for block B's.
-#ifndef MIP_PAIR_MIN_AREA
-#define MIP_PAIR_MIN_AREA 32  // smallest CU area walked in block pairs (A/B knob; 33: 4x8 unpaired, -0.6 %)
-#endif
+constexpr int kPairMinArea = 32;  // smallest CU area walked in block pairs (33: 4x8 unpaired, -0.6 %)
 template <int W, int H, int V>
-constexpr bool kPaired = Geo<W, H, V>::SID != 0 && W * H >= MIP_PAIR_MIN_AREA && V == kClassV[size_class(W, H)] &&
+constexpr bool kPaired = Geo<W, H, V>::SID != 0 && W * H >= kPairMinArea && V == kClassV[size_class(W, H)] &&
                          ((Geo<W, H, V>::CHUNKED && !kSpanChunks ? Geo<W, H, V>::CROWS * Geo<W, H, V>::UV
                                                                  : Geo<W, H, V>::KV * Geo<W, H, V>::UV) / 4) % 2 == 0;
 
@@ -1174,9 +1113,9 @@ __device__ __forceinline__ void phase_a(const Ctx &x, int lane, int ncu, int q, 
       pofs = HALF ? -8 * chunk : 0;  // rows 2 * chunk, 2 * chunk + 1 -> chunk rows 0, 1
     }
     const h4 av = *reinterpret_cast<const h4 *>(abase + jofs * 16);
-    // classes with many column sets (one row block): all B operands read up front, so the
-    // MFMAs do not each wait for an LDS read (partial tasks read unused CU-table entries)
-    constexpr bool BATCH_B = NRB == 1 && NCS >= MIP_PHASEA_BATCH_NCS;
+    // classes with two or more column sets (one row block): all B operands read up front, so
+    // the MFMAs do not each wait for an LDS read (partial tasks read unused CU-table entries)
+    constexpr bool BATCH_B = NRB == 1 && NCS >= 2;
     h4 bvs[BATCH_B ? NCS : 1];
     if constexpr (BATCH_B) {
 #pragma unroll
@@ -1286,22 +1225,14 @@ __device__ __forceinline__ uint32_t group_sum(uint32_t v) {
 // the sum, so the compiler sinks that add under the branch's exec mask, where the DPP read
 // cannot fold into it (v_mov_b32_dpp + v_add_u32 instead of one v_add_u32_dpp: 4 VALU per
 // mode pair in every class with more than one lane per CU).
-#ifndef MIP_PIN_SUMS
-#define MIP_PIN_SUMS 1  // A/B knob
-#endif
 __device__ __forceinline__ uint32_t pin_sum(uint32_t v) {
-#if MIP_PIN_SUMS
   asm volatile("; pin" : "+v"(v));
-#endif
   return v;
 }
 
 // Cost-table stores of a task: a buffer descriptor over the CTU's block (uniform per
 // item), the CU's byte offset as the per-lane VGPR offset (per task) and the mode pair's
 // offset as the scalar offset (per pair) -- the pair loop computes no per-lane address.
-#ifndef MIP_COST_STORE_AUX
-#define MIP_COST_STORE_AUX 0  // A/B: cache-policy bits of the cost-row stores
-#endif
 struct CtuRows {
   __amdgpu_buffer_rsrc_t r;
   __device__ __forceinline__ explicit CtuRows(int32_t *ctu_block) {
@@ -1309,7 +1240,9 @@ struct CtuRows {
   }
   __device__ __forceinline__ void store(uint32_t cu_ofs, int mq, int v0, int v1) const {
     typedef unsigned int v2u __attribute__((ext_vector_type(2)));
-    __builtin_amdgcn_raw_buffer_store_b64((v2u){(unsigned)v0, (unsigned)v1}, r, (int)cu_ofs, mq * 4, MIP_COST_STORE_AUX);
+    // (aux 0, the default cache policy: non-temporal stores ran at 4790 frames/s -- every 8-byte
+    // store its own memory write -- and sc0 changed nothing)
+    __builtin_amdgcn_raw_buffer_store_b64((v2u){(unsigned)v0, (unsigned)v1}, r, (int)cu_ofs, mq * 4, 0);
   }
 };
 
@@ -1406,7 +1339,7 @@ __device__ __forceinline__ void run_task(const Ctx &x, const RefTile<LAT> &rt_ti
   wave_lds_sync();
 
   uint32_t best = 0xffffffffu;  // DEC (decisions only): argmin over the task's pairs, cost << 5 | mode
-  constexpr bool PAIRED = MIP_PAIR_BLOCKS && kPaired<W, H, V>;
+  constexpr bool PAIRED = kPaired<W, H, V>;
 #pragma unroll 1
   for (int q = task.q0; q < task.q1; q++) {
     std::conditional_t<PAIRED, PairAcc, std::conditional_t<(W * H <= 32), PackedAcc, Acc>> acc;
@@ -1606,11 +1539,8 @@ struct WindowStager {
 // frame are not the reference's (the packed 16-bit / f16 arithmetic is sized for 10 bits), so
 // the host reports the search as failed.  Rare path: one plain store per offending thread.
 // Merged chunks (SearchArgs::frame_status): the frame's own call's status set.
-#ifndef MIP_FRAME_STATUS
-#define MIP_FRAME_STATUS 1  // A/B: 0 = one status set per launch (wrong statuses in merged launches)
-#endif
 __device__ __forceinline__ void flag_above_10_bits(uint32_t bits, const SearchArgs &a, int frame, int word) {
-  if (bits & kAbove10Bits) (MIP_FRAME_STATUS && a.frame_status ? a.frame_status[frame] : a.status)[word] = 1u;
+  if (bits & kAbove10Bits) (a.frame_status ? a.frame_status[frame] : a.status)[word] = 1u;
 }
 
 template <int NT>
@@ -1714,13 +1644,36 @@ __device__ __forceinline__ void stage_lattice(uint16_t *dst, const uint16_t *fra
 // the staging altogether measured +1.2 %).  Taking the next item early would unbalance the
 // end of a launch (a reserved item waits while other workgroups run dry: 16-frame launches
 // -1.4 % when every item was prefetched), so in the last two rounds of items the next one is
-// taken after the current one instead; launches with fewer than MIP_PREFETCH_MIN_ITEMS items
+// taken after the current one instead; launches with fewer than kPrefetchMinItems items
 // per workgroup do not prefetch at all (1-frame launches measured -9 % with the prefetching
 // kernel).  The ALT lattice leaves no LDS for a second window.
-template <bool ALT, bool PF, int NW = kSearchWaves>
-constexpr int kOrgTiles = (PF || NW == kWideWaves) && !ALT ? 2 : 1;  // (16 waves: pair mode)
 constexpr int kCounterWords = 12;  // [parity]: next task, finished waves, item, item taken late;
                                    // [8]: chunks this workgroup has found empty (take_item)
+
+// LDS of one workgroup of mip_search_kernel<ALT, *, PF, NW> (its dynamic shared memory): the
+// byte offsets of its areas, in this order after the windows at 0, and the total.
+struct LdsLayout {
+  size_t lattice;   // ALT: the reference lattice (kLatElems samples)
+  size_t tables;    // the MIP tables (kTableBytes, copied from SearchArgs::tables)
+  size_t zero;      // kZeroBytes of zeros
+  size_t waves;     // nw wave-private areas of kWaveStride bytes
+  size_t counters;  // kCounterWords
+  size_t bytes;
+};
+constexpr LdsLayout lds_layout(bool alt, bool pf, int nw) {
+  const int windows = (pf || nw == kWideWaves) && !alt ? 2 : 1;  // (16 waves: pair mode)
+  LdsLayout l{};
+  l.lattice = (size_t)windows * kTileElems * 2;
+  l.tables = l.lattice + (alt ? kLatElems * 2 : 0);
+  l.zero = l.tables + kTableBytes;
+  l.waves = l.zero + kZeroBytes;
+  l.counters = l.waves + (size_t)nw * kWaveStride;
+  l.bytes = l.counters + kCounterWords * 4;
+  return l;
+}
+// two windows, the tables and the wave areas (12 x 4 KB or 8 x 6 KB) fill 81 648 of the 81 920
+// bytes a workgroup may take with two per CU
+static_assert(lds_layout(false, true, kSearchWaves).bytes * 2 <= 160 * 1024, "two workgroups per CU");
 
 // The launch's items in kQueueChunks contiguous chunks (fewer if the grid is smaller), chunk
 // c = [chunk_begin(c), chunk_begin(c + 1)) with its own counter a.queue[c].  Workgroup b
@@ -1791,7 +1744,7 @@ __device__ __forceinline__ void dispatch_task(const Ctx &x, const RefTile<ALT> &
 #define MIP_CASE(idx, W, H)                                                \
   case idx:                                                                \
     static_assert(kClassW[idx] == W && kClassH[idx] == H, "class table");  \
-    if constexpr ((MIP_ONLY_CLASS < 0 || MIP_ONLY_CLASS == idx) && !((MIP_SKIP_CLASSES >> idx) & 1)) \
+    if constexpr (MIP_ONLY_CLASS < 0 || MIP_ONLY_CLASS == idx)             \
       run_task<W, H, kClassV[idx], ALT, DEC>(x, rt, task, lane);           \
     break;
     MIP_CASE(0, 64, 64) MIP_CASE(1, 32, 32) MIP_CASE(2, 32, 16) MIP_CASE(3, 16, 32)
@@ -1806,7 +1759,7 @@ __device__ __forceinline__ void dispatch_task(const Ctx &x, const RefTile<ALT> &
 #define MIP_CASE_TR(idx, W, H)                                                    \
   case idx:                                                                       \
     static_assert(kClassW[idx] == W && kClassH[idx] == H && kClassTR[idx], "class table"); \
-    if constexpr ((MIP_ONLY_CLASS < 0 || MIP_ONLY_CLASS == idx) && !((MIP_SKIP_CLASSES >> idx) & 1)) \
+    if constexpr (MIP_ONLY_CLASS < 0 || MIP_ONLY_CLASS == idx)                    \
       run_task<W, H, kClassV[idx], ALT, DEC, true>(x, rt, task, lane);            \
     break;
     // transposed classes: wide CUs searched as their transposes
@@ -1929,43 +1882,26 @@ __device__ __forceinline__ void pair_loop(const SearchArgs &a, uint16_t *org_buf
 
 // DEC: decisions only -- no cost table, per-CU decisions (SearchArgs::best_mode / best_cost).
 // NW: waves per workgroup (kSearchWaves; kWideWaves: one workgroup per CU, small launches)
-#ifndef MIP_WAVES_PER_EU
-#define MIP_WAVES_PER_EU (MIP_SIX_WAVES ? 6 : 4)  // HIP-Clang: the second launch bound is the minimum waves per SIMD
-#endif
-// Six waves per SIMD: the MIP tables are read from global memory (L1 / L2) instead of LDS
-// and the search never prefetches the next window (no LDS for a second one).
-#ifndef MIP_TABLES_GLOBAL
-#define MIP_TABLES_GLOBAL 0  // A/B: the MIP tables from global memory at four waves per SIMD too
-#endif
-constexpr bool kTablesInLds = (!MIP_SIX_WAVES || MIP_SIX_WAVES == 3) && !MIP_TABLES_GLOBAL;
-// (MIP_SIX_WAVES 3: two windows, the tables and 12 x 4 KB of wave areas fill 81 648 of the
-// 81 920 bytes a workgroup may take with two per CU)
-#ifndef MIP_S6_PF
-#define MIP_S6_PF 1  // A/B: next-item prefetch in the MIP_SIX_WAVES 3 build
-#endif
-#define MIP_PF_KERNEL (!MIP_SIX_WAVES || (MIP_SIX_WAVES == 3 && MIP_S6_PF))
-constexpr bool kPrefetchKernel = MIP_PF_KERNEL;
+// (HIP-Clang: the second launch bound is the minimum waves per SIMD)
+constexpr int kWavesPerSimd = MIP_SIX_WAVES == 3 ? 6 : 4;
 template <bool ALT, bool DEC, bool PF_, int NW>
-__global__ __launch_bounds__(64 * NW, NW == kWideWaves ? 4 : MIP_WAVES_PER_EU) void mip_search_kernel(SearchArgs a) {
-  constexpr bool PF = PF_ && !ALT && NW == kSearchWaves && kPrefetchKernel;
+__global__ __launch_bounds__(64 * NW, NW == kWideWaves ? 4 : kWavesPerSimd) void mip_search_kernel(SearchArgs a) {
+  constexpr bool PF = PF_ && !ALT && NW == kSearchWaves;
+  constexpr LdsLayout L = lds_layout(ALT, PF, NW);
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  uint16_t *org_buf = reinterpret_cast<uint16_t *>(smem);  // kOrgTiles windows
-  uint16_t *lattice = org_buf + kOrgTiles<ALT, PF, NW> * kTileElems;
-  uint8_t *tab = smem + (kOrgTiles<ALT, PF, NW> * kTileElems + (ALT ? kLatElems : 0)) * 2;
-  uint8_t *zero = tab + (kTablesInLds ? kTableBytes : 0);
-  uint8_t *waves = zero + kZeroBytes;
-  uint32_t *counters = reinterpret_cast<uint32_t *>(waves + NW * kWaveStride);
-  const uint8_t *w = kTablesInLds ? tab : reinterpret_cast<const uint8_t *>(a.tables);
+  uint16_t *org_buf = reinterpret_cast<uint16_t *>(smem);  // one or two windows
+  uint16_t *lattice = reinterpret_cast<uint16_t *>(smem + L.lattice);
+  uint8_t *tab = smem + L.tables, *zero = smem + L.zero, *waves = smem + L.waves;
+  uint32_t *counters = reinterpret_cast<uint32_t *>(smem + L.counters);
 
-  if constexpr (kTablesInLds)
-    for (int i = threadIdx.x; i < kTableBytes / 16; i += blockDim.x)
-      reinterpret_cast<uint4 *>(tab)[i] = a.tables[i];
+  for (int i = threadIdx.x; i < kTableBytes / 16; i += blockDim.x)
+    reinterpret_cast<uint4 *>(tab)[i] = a.tables[i];
   for (int i = threadIdx.x; i < kZeroBytes / 16; i += blockDim.x)
     reinterpret_cast<uint4 *>(zero)[i] = make_uint4(0, 0, 0, 0);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
 
   if (NW == kWideWaves && !ALT && !PF && a.nonempty > 0) {  // uniform: pair mode
-    pair_loop<DEC>(a, org_buf, w, zero, waves, counters, wave, lane);
+    pair_loop<DEC>(a, org_buf, tab, zero, waves, counters, wave, lane);
   } else {
   // Persistent workgroups (as many as are resident) take items = (frame, CTU, quadrant,
   // slice) from a device-wide queue (take_item), in order: the hardware's static round-robin of
@@ -2006,7 +1942,7 @@ __global__ __launch_bounds__(64 * NW, NW == kWideWaves ? 4 : MIP_WAVES_PER_EU) v
         __syncthreads();
       }
 
-      const Ctx x{&a, org, ref, w, zero, waves + wave * kWaveStride, ctu, frame, fx0, fy0};
+      const Ctx x{&a, org, ref, tab, zero, waves + wave * kWaveStride, ctu, frame, fx0, fy0};
       const RefTile<ALT> rt{ref};
       // Waves take the item's tasks (longest first) from an LDS counter, so early
       // finishers pick up the slack of waves the SIMD arbiter serves later.
@@ -2017,20 +1953,11 @@ __global__ __launch_bounds__(64 * NW, NW == kWideWaves ? 4 : MIP_WAVES_PER_EU) v
         if (lane == 0) tn = atomicAdd(next_task, 1u);
         const int t = (int)__builtin_amdgcn_readfirstlane(tn);
         if (t >= ntasks) break;
-#if MIP_PRIO_BALANCE
-        // Two workgroups share a CU, and the SIMD arbiter serves the older waves first: in a
-        // small launch the first workgroup of a CU finished its item in 98 us while the
-        // second, starved, took 170 us (profiles/r04_item_timeline_1frame.csv).  A wave's
-        // priority follows the share of its item still to do, so the workgroup that is
-        // behind is served first and the two finish together.
-        {
-          const int rem4 = 4 * (ntasks - t);  // uniform
-          if (rem4 > 3 * ntasks) __builtin_amdgcn_s_setprio(3);
-          else if (rem4 > 2 * ntasks) __builtin_amdgcn_s_setprio(2);
-          else if (rem4 > ntasks) __builtin_amdgcn_s_setprio(1);
-          else __builtin_amdgcn_s_setprio(0);
-        }
-#endif
+        // (Two workgroups share a CU and the SIMD arbiter serves the older waves first: in a
+        // small launch the first workgroup of a CU finished its item in 98 us, the second,
+        // starved, in 170 us, profiles/r04_item_timeline_1frame.csv.  Letting a wave's priority
+        // follow the share of its item still to do, s_setprio, measured -1.7 % at 384 frames,
+        // -1.5 % at 32, 1 frame 0.184 -> 0.177 ms: not done.)
         const uint64_t c0 = clk ? __builtin_readcyclecounter() : 0;
         const WaveTask task = a.tasks[tbase + t];
         dispatch_task<ALT, DEC>(x, rt, task, lane);
@@ -2058,9 +1985,9 @@ __global__ __launch_bounds__(64 * NW, NW == kWideWaves ? 4 : MIP_WAVES_PER_EU) v
           const ItemPos np(a, nitem);
           const uint16_t *nframe = a.orig + (size_t)np.frame * a.width * a.height;
           uint16_t *dst = org_buf + (par ^ 1) * kTileElems;
-          // loads in flight MIP_PF_BATCH at a time, then their stores
+          // window loads in flight NB at a time per lane, then their stores (6: -0.3 %)
           const WindowStager<64> st(nframe, a.width, a.height, np.fx0, np.fy0, lane);
-          constexpr int NL = WindowStager<64>::N, NB = MIP_PF_BATCH;
+          constexpr int NL = WindowStager<64>::N, NB = 10;
           uint32_t bits = 0;
 #pragma unroll
           for (int k0 = 0; k0 < NL; k0 += NB) {
@@ -2106,122 +2033,37 @@ __global__ __launch_bounds__(64 * NW, NW == kWideWaves ? 4 : MIP_WAVES_PER_EU) v
   }
 }
 
-// Decision list of one CU: the k lowest-cost of its M modes (ties to the lower mode), by
-// repeated selection over the row held in registers; 0xff / kUnavailable past the M modes
-// and for unavailable CUs (every entry of such a row is kUnavailable).
-template <int M>
-__device__ __forceinline__ void topk_row(const int32_t *row, int k, uint8_t *mo, int32_t *co) {
-  int v[M];
-#pragma unroll
-  for (int m = 0; m < M; m += 4) {  // rows start 16-byte aligned (12, 16 or 32 entries per CU)
-    const int4 q = *reinterpret_cast<const int4 *>(row + m);
-    v[m] = q.x, v[m + 1] = q.y, v[m + 2] = q.z, v[m + 3] = q.w;
-  }
-  const bool unavailable = v[0] == kUnavailable;
-  uint32_t used = 0;
-  for (int r = 0; r < k; r++) {
-    int best = 0, bc = 0;
-    bool found = false;
-#pragma unroll
-    for (int m = 0; m < M; m++)
-      if (!((used >> m) & 1) && (!found || v[m] < bc)) best = m, bc = v[m], found = true;
-    const bool ok = found && !unavailable;
-    if (ok) used |= 1u << best;
-    if (mo) mo[r] = ok ? (uint8_t)best : 0xff;
-    if (co) co[r] = ok ? bc : kUnavailable;
-  }
+// The kernel instance of a launch, chosen here and nowhere else: alternative references and
+// wide launches have no prefetching instance (pf is false for them).
+using SearchKernel = void (*)(SearchArgs);
+template <bool ALT, bool PF, int NW>
+SearchKernel search_kernel(bool dec) {
+  return dec ? mip_search_kernel<ALT, true, PF, NW> : mip_search_kernel<ALT, false, PF, NW>;
 }
-
-// Per-CU decision lists (k = 1: the argmin).
-#if !MIP_FOUR_WAVE_TWIN
-__global__ __launch_bounds__(256) void best_mode_kernel(BestArgs a) {
-  const int g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= a.total_cus) return;
-  const int ctu = g / MIP_CUS_PER_CTU;
-  int r = g - ctu * MIP_CUS_PER_CTU, s = 0;
-#pragma unroll
-  for (int step = 32; step; step >>= 1)  // last shape whose first CU is <= r
-    if (s + step < MIP_NUM_SHAPES && c_shape_start.v[s + step] <= r) s += step;
-  r -= c_shape_start.v[s];
-  const mip_shape_desc sd = c_shapes[s];
-  const int32_t *row = a.cost + (size_t)ctu * MIP_COSTS_PER_CTU + sd.cost_offset + (size_t)r * 2 * sd.modes;
-  uint8_t *mo = a.best_mode ? a.best_mode + (size_t)g * a.k : nullptr;
-  int32_t *co = a.best_cost ? a.best_cost + (size_t)g * a.k : nullptr;
-  switch (sd.modes) {
-    case 6: topk_row<12>(row, a.k, mo, co); break;
-    case 8: topk_row<16>(row, a.k, mo, co); break;
-    default: topk_row<32>(row, a.k, mo, co); break;
-  }
+SearchKernel search_kernel(bool alt, bool dec, bool pf, bool wide) {
+  constexpr int S = kSearchWaves, L = kWideWaves;
+  if (wide) return alt ? search_kernel<true, false, L>(dec) : search_kernel<false, false, L>(dec);
+  if (alt) return search_kernel<true, false, S>(dec);
+  return pf ? search_kernel<false, true, S>(dec) : search_kernel<false, false, S>(dec);
 }
-
-// Split CUs of decisions-only searches: all ones before the search (init), packed argmin ->
-// decision list of length 1 after it (the layout of best_mode_kernel with k = 1).
-template <bool INIT>
-__global__ __launch_bounds__(256) void dec_split_kernel(SplitArgs a, int total) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= total) return;
-  const int j = t % a.max_split, r = t / a.max_split, ctu = a.ctu0 + r % a.nrange, frame = r / a.nrange;
-  const int v = a.ctu_var[ctu], b = a.split_begin[v];
-  if (j >= a.split_begin[v + 1] - b) return;
-  const size_t g = ((size_t)frame * a.nctus + ctu) * MIP_CUS_PER_CTU + a.split[b + j];
-  if (INIT) {
-    if (a.acc) a.acc[g] = ~0u;
-    else a.best_cost[g] = -1;
-  } else {
-    uint32_t p;
-    if (a.acc) {
-      p = a.acc[g];
-      a.acc[g] = ~0u;  // initialised for the next launch
-    } else {
-      p = (uint32_t)a.best_cost[g];
-    }
-    const bool ok = p != 0xffffffffu;
-    if (a.best_mode) a.best_mode[g] = ok ? (uint8_t)(p & 31) : (uint8_t)0xff;
-    a.best_cost[g] = ok ? (int32_t)(p >> 5) : kUnavailable;
-  }
-}
-
-#endif  // !MIP_FOUR_WAVE_TWIN
 }  // namespace
-
-static constexpr size_t search_lds_bytes_c(bool alt, bool pf, int waves) {  // (internal: differs per compilation)
-  return (size_t)(((pf || waves == kWideWaves) && !alt ? 2 : 1) * kTileElems + (alt ? kLatElems : 0)) * 2 +
-         (kTablesInLds ? kTableBytes : 0) + kZeroBytes + (size_t)waves * kWaveStride + kCounterWords * 4;
-}
-size_t search_lds_bytes(bool alt, bool pf, int waves) {
-  const bool two = (pf || waves == kWideWaves) && !alt;  // kOrgTiles
-  return (size_t)((two ? 2 : 1) * kTileElems + (alt ? kLatElems : 0)) * 2 + (kTablesInLds ? kTableBytes : 0) + kZeroBytes +
-         (size_t)waves * kWaveStride + kCounterWords * 4;
-}
-
-static_assert(!MIP_SIX_WAVES || MIP_SIX_WAVES == 2 ||
-                  search_lds_bytes_c(false, MIP_PF_KERNEL, kSearchWaves) * 2 <= 160 * 1024, "two workgroups per CU");
-
-template <bool ALT, bool DEC, bool PF, int NW>
-static int resident_per_cu() {
-  int per_cu = 0;
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mip_search_kernel<ALT, DEC, PF, NW>, 64 * NW,
-                                                      search_lds_bytes(ALT, PF, NW)) == hipSuccess ? per_cu : 0;
-}
 
 int search_resident_groups(bool alt, bool wide) {
   int dev = 0, cus = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
     return 0;
-  // every variant of a width shares the grid size
-  constexpr int S = kSearchWaves, L = kWideWaves;
-  int per_cu;
   if (wide && MIP_FOUR_WAVE_TWIN) return 0;
-  if (wide && !MIP_FOUR_WAVE_TWIN)
-    per_cu = alt ? std::min(resident_per_cu<true, false, false, L>(), resident_per_cu<true, true, false, L>())
-                 : std::min(resident_per_cu<false, false, false, L>(), resident_per_cu<false, true, false, L>());
-  else
-    per_cu = alt ? std::min(resident_per_cu<true, false, false, S>(), resident_per_cu<true, true, false, S>())
-                 : std::min({resident_per_cu<false, false, false, S>(), resident_per_cu<false, true, false, S>(),
-#if MIP_PREFETCH_MIN_ITEMS < 1000000 && MIP_PF_KERNEL  // (builds that never prefetch: the others' grid)
-                             resident_per_cu<false, false, true, S>(), resident_per_cu<false, true, true, S>()
-#endif
-                             });
+  const int nw = wide ? kWideWaves : kSearchWaves;
+  // every variant of a width shares the grid size: the fewest any of its instances allows
+  int per_cu = 1 << 30;
+  for (int pf = 0; pf <= (alt || wide ? 0 : 1); pf++)
+    for (int dec = 0; dec <= 1; dec++) {
+      int n = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, search_kernel(alt, dec, pf, wide), 64 * nw,
+                                                       lds_layout(alt, pf, nw).bytes) != hipSuccess)
+        return 0;
+      per_cu = std::min(per_cu, n);
+    }
   return per_cu >= 1 ? cus * per_cu : 0;
 }
 
@@ -2239,7 +2081,7 @@ hipError_t launch_search(const SearchArgs &args, int nframes, bool alt_refs, int
   const char *qc = getenv("MIPGPU_QUEUE_CHUNKS");  // tuning knob
   a.chunks = qc && atoi(qc) >= 1 && atoi(qc) <= kQueueChunks
                  ? (uint32_t)atoi(qc)
-                 : (a.nitems >= (uint32_t)MIP_PREFETCH_MIN_ITEMS * (uint32_t)resident ? (uint32_t)kQueueChunks : 1u);
+                 : (a.nitems >= (uint32_t)kPrefetchMinItems * (uint32_t)resident ? (uint32_t)kQueueChunks : 1u);
   a.nframes = (uint32_t)nframes;
   if (a.chunks > 1 || a.ctu0 != 0 || a.nrange != a.nctus) a.order = nullptr;  // large or range launches
   if (!wide || alt_refs || !a.order || a.chunks != 1 || a.nonempty > a.nitems) a.nonempty = 0;  // pair mode
@@ -2247,63 +2089,20 @@ hipError_t launch_search(const SearchArgs &args, int nframes, bool alt_refs, int
   const int groups = std::min<long long>(env && atoi(env) > 0 ? atoi(env) : resident, a.nitems);
   const bool dec = a.cost == nullptr;
   if (dec && (!a.best_cost || !a.dfill_begin)) return hipErrorInvalidValue;
-  const bool pf = kPrefetchKernel && !alt_refs && !wide && a.nitems >= (uint32_t)MIP_PREFETCH_MIN_ITEMS * (uint32_t)groups;
-  const size_t lds = search_lds_bytes(alt_refs, pf, wide ? kWideWaves : kSearchWaves);
+  const bool pf = !alt_refs && !wide && a.nitems >= (uint32_t)kPrefetchMinItems * (uint32_t)groups;
+  const int nw = wide ? kWideWaves : kSearchWaves;
+  const size_t lds = lds_layout(alt_refs, pf, nw).bytes;
   if (info)  // (the instance chosen below, and the launch modes the kernel sees)
-    *info = SearchLaunchInfo{wide ? kWideWaves : kSearchWaves, alt_refs, dec, pf, a.nonempty > 0, a.chunks > 1,
-                             a.order != nullptr};
-  const dim3 grid(groups);
-  constexpr int S = kSearchWaves, L = kWideWaves;
-  (void)L;
-  auto go = [&](auto kern, const dim3 &block) {  // with `done`: the dispatch itself records it (no marker packet)
-    if (done) hipExtLaunchKernelGGL(kern, grid, block, (uint32_t)lds, s, nullptr, done, 0u, a);
-    else hipLaunchKernelGGL(kern, grid, block, lds, s, a);
-  };
-  if (wide) {
+    *info = SearchLaunchInfo{nw, alt_refs, dec, pf, a.nonempty > 0, a.chunks > 1, a.order != nullptr};
 #if MIP_FOUR_WAVE_TWIN
-    return hipErrorInvalidValue;  // (the twin serves batched-width launches only)
-#else
-    const dim3 block(64 * L);
-    if (alt_refs) {
-      if (dec) go(mip_search_kernel<true, true, false, L>, block);
-      else go(mip_search_kernel<true, false, false, L>, block);
-    } else {
-      if (dec) go(mip_search_kernel<false, true, false, L>, block);
-      else go(mip_search_kernel<false, false, false, L>, block);
-    }
-    return hipGetLastError();
+  if (wide) return hipErrorInvalidValue;  // (the twin serves batched-width launches only)
 #endif
-  }
-  const dim3 block(64 * S);
-  if (alt_refs) {
-    if (dec) go(mip_search_kernel<true, true, false, S>, block);
-    else go(mip_search_kernel<true, false, false, S>, block);
-  } else if (pf) {
-    if (dec) go(mip_search_kernel<false, true, true, S>, block);
-    else go(mip_search_kernel<false, false, true, S>, block);
-  } else {
-    if (dec) go(mip_search_kernel<false, true, false, S>, block);
-    else go(mip_search_kernel<false, false, false, S>, block);
-  }
+  const SearchKernel kern = search_kernel(alt_refs, dec, pf, wide);
+  const dim3 grid(groups), block(64 * nw);
+  // with `done`: the dispatch itself records it (no marker packet)
+  if (done) hipExtLaunchKernelGGL(kern, grid, block, (uint32_t)lds, s, nullptr, done, 0u, a);
+  else hipLaunchKernelGGL(kern, grid, block, lds, s, a);
   return hipGetLastError();
 }
-
-#if !MIP_FOUR_WAVE_TWIN
-hipError_t launch_dec_split(const SplitArgs &a, int nframes, bool init, hipStream_t s) {
-  if (a.max_split < 1) return hipSuccess;  // no split CUs
-  const long long total = (long long)nframes * a.nrange * a.max_split;
-  if (!a.best_cost || !a.split || total >= (1LL << 31)) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)((total + 255) / 256));
-  if (init) hipLaunchKernelGGL(dec_split_kernel<true>, grid, dim3(256), 0, s, a, (int)total);
-  else hipLaunchKernelGGL(dec_split_kernel<false>, grid, dim3(256), 0, s, a, (int)total);
-  return hipGetLastError();
-}
-
-hipError_t launch_best_modes(const BestArgs &a, hipStream_t s) {
-  if (a.k < 1 || a.k > kMaxBestK) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(best_mode_kernel, dim3((a.total_cus + 255) / 256), dim3(256), 0, s, a);
-  return hipGetLastError();
-}
-#endif  // !MIP_FOUR_WAVE_TWIN
 
 }  // namespace mipgpu

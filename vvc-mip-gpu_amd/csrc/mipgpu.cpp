@@ -706,9 +706,6 @@ namespace {
 // CU count limit of one launch (int32 indices in the decision-list kernel).
 constexpr long long kMaxCus = (1LL << 31) - 256;
 
-// Items per workgroup from which a launch cuts its queue into XCD chunks and prefetches
-// (mip_search.hip MIP_PREFETCH_MIN_ITEMS); below it, items are taken longest first.
-constexpr int kSmallLaunchItemsPerGroup = 32;
 // Per-item cost beyond its tasks (window staging, barriers, fills), in the task cost
 // model's units (pair_cost: VALU instructions per lane).
 constexpr double kItemOverhead = 600.0;
@@ -790,7 +787,7 @@ bool wide_launch(long long items1, int cus) {
 }
 
 // Work lists for a launch of `nframes`: items (quadrant x slice) for the persistent grid.
-// Large launches (>= kSmallLaunchItemsPerGroup items per workgroup at one slice): one slice.
+// Large launches (>= kPrefetchMinItems items per workgroup at one slice): one slice.
 // Small ones take their items longest first, on 8- or 16-wave workgroups (wide_launch); the
 // slice count is the one whose predicted makespan (lpt_makespan, per frame count, cached) is
 // the shortest.  (Before the LPT order: 1 frame -> 2 slices 5076 frames/s at 1080p (1: 4842,
@@ -798,7 +795,7 @@ bool wide_launch(long long items1, int cus) {
 const mip_engine::Work &pick_work(mip_engine *e, int nframes, int nrange, bool alt) {
   const int groups = e->resident[alt ? 1 : 0];
   const long long items1 = 4LL * nrange * nframes;  // items at one slice
-  if (nrange != e->nctus || items1 >= (long long)kSmallLaunchItemsPerGroup * groups || !lpt_order_enabled()) {
+  if (nrange != e->nctus || items1 >= (long long)mipgpu::kPrefetchMinItems * groups || !lpt_order_enabled()) {
     const int want = items1 < 1000 && nrange != e->nctus ? 2 : 1;
     const mip_engine::Work *best = nullptr;
     for (const mip_engine::Work &w : e->work)
@@ -1417,7 +1414,7 @@ static int search_device_impl(mip_engine *e, const uint16_t *d_frames, const uin
   // or -- MIPGPU_PIPE_KERNEL=6 -- one 12-wave workgroup per CU (8 queued one-frame
   // decisions-only calls 4740 -> 5100 frames/s, 32 calls 5550 -> 6340).
   const bool pipe_small = alternating && !work.wide &&
-                          (long long)4 * work.slices * nrange * nframes < (long long)kSmallLaunchItemsPerGroup * resident;
+                          (long long)4 * work.slices * nrange * nframes < (long long)mipgpu::kPrefetchMinItems * resident;
   const int pk = pipe_kernel();
   // (decisions-only pipeline chunks of any size too: their downloads -- blit kernels on torch's
   // runtime -- and split unpacking run beside the next chunk's search; 8 queued 128-frame
