@@ -750,7 +750,7 @@ def test_small_launch_shapes_agree(gpu_available, monkeypatch, w, h, n, filt, k)
             outs.append(((wide, pair, order), full, dec))
             # what ran: MIPGPU_WIDE=1 with the longest-first order gives 16-wave workgroups, in
             # pair mode exactly with original references and MIPGPU_PAIR on; MIPGPU_ORDER=0
-            # takes the large-launch work lists (mipgpu.cpp pick_work), i.e. never 16 waves
+            # takes the large-launch work lists (mipgpu.cpp pick_work, work_plan.h closest_slices), i.e. never 16 waves
             launches = sum(v for k, v in d.items() if isinstance(k, tuple))
             if wide == "1" and order == "1":
                 assert _waves(d) == {16}, (wide, pair, order, d)

@@ -5,7 +5,7 @@ served the call.
 libmipgpu.so holds 16 instances: the 12-wave kernel ({orig, alt} x {table, decisions}, orig
 also prefetching), the 16-wave kernel of small launches ({orig, alt} x {table, decisions}) and
 the 8-wave four-wave twin of the host pipeline (as the 12-wave set).  Which one a call gets is
-decided by its size, its API and a handful of knobs (mipgpu.cpp pick_work / wide_launch /
+decided by its size, its API and a handful of knobs (mipgpu.cpp pick_work / wide_launch over work_plan.h,
 pipe_kernel, mip_search.hip launch_search); CELLS names, per instance, one recipe of knobs
 that reaches it on 264x200 frames -- 3x2 CTUs, partial CTUs on both axes, a width that is not a
 multiple of 128 (wrapped reads; with alternative references the CUs that read the last two

@@ -1,5 +1,5 @@
 """mip_unavailable_cus (host only, no GPU): the CUs an engine reports as MIP_COST_UNAVAILABLE,
-restated in the product (mipgpu.cpp filter_poison) from the reference's tile addressing,
+restated in the product (work_plan.h filter_poison) from the reference's tile addressing,
 against the oracle's model of the same (mipo_filter_frame_ex poison bit + mipo_ref_undefined_cus,
 itself pinned by the fill experiment of tools/ref_golden.py)."""
 import numpy as np

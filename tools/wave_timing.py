@@ -3,7 +3,7 @@
 
 Runs one warm-up and one instrumented 1080p batch.  Reports, per size class, the mean wall
 cycles of its tasks (under the kernel's normal co-residency) and per (task, mode pair) --
-the data the host's task cost model (mipgpu.cpp pair_cost) is checked against -- and the
+the data the host's task cost model (work_plan.h pair_cost) is checked against -- and the
 workgroup's summed task cycles per quadrant."""
 import json
 import os

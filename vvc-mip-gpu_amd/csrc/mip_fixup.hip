@@ -4,7 +4,7 @@
 // The search kernel (mip_search.hip) packs two modes into 16-bit halves and feeds the MFMA
 // with f16 samples: both are exact for 10-bit reference samples only.  At frame widths that
 // are not multiples of 128 the reference's separable filters give the last one or two frame
-// columns values up to ~1.7 x 1023 (mipgpu.cpp reads_last_columns), so with alternative
+// columns values up to ~1.7 x 1023 (work_plan.h reads_last_columns), so with alternative
 // references the CUs that read those columns are left out of the search kernel's work lists
 // and searched here, one 64-thread workgroup per (frame, CU), in plain 32-bit integer
 // arithmetic -- the reference's own semantics:

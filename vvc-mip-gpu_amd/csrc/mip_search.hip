@@ -1589,7 +1589,7 @@ struct ItemPos {
 // by linear index like the window (frame_chunk).
 // check: caller-supplied references (SearchArgs::check_refs) must be 10-bit too, except frame
 // columns W-2, W-1 at widths that are not multiples of 128, whose CUs the exact fixup kernel
-// searches (mipgpu.cpp ctu_variants / reads_last_columns).  Samples are addressed linearly,
+// searches (work_plan.h ctu_variants / reads_last_columns).  Samples are addressed linearly,
 // so a chunk's frame column is its x modulo the width.
 template <int NT>
 __device__ __forceinline__ void stage_lattice(uint16_t *dst, const uint16_t *frame, int width, int height,
@@ -1928,7 +1928,7 @@ __global__ __launch_bounds__(64 * NW, NW == kWideWaves ? 4 : kWavesPerSimd) void
     const ItemPos ip(a, item);
     const int ctu = ip.ctu, frame = ip.frame, slice = ip.slice, quad = ip.quad, fx0 = ip.fx0, fy0 = ip.fy0;
     const size_t fofs = (size_t)frame * a.width * a.height;
-    const int var = a.ctu_var[ctu];  // work / fill lists of the CTU's variant (mipgpu.cpp ctu_variants)
+    const int var = a.ctu_var[ctu];  // work / fill lists of the CTU's variant (work_plan.h ctu_variants)
     const int vq = var * 4 + quad, list = vq * a.slices + slice;
     const int tbase = a.list_begin[list], ntasks = a.list_begin[list + 1] - tbase;
     uint16_t *org = org_buf + (PF ? par * kTileElems : 0);

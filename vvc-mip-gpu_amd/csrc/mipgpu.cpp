@@ -1,11 +1,11 @@
-// mipgpu.cpp -- C-ABI engine (include/mipgpu.h): device set-up, buffers, work lists and
-// the per-batch launch sequence that replaces main.cpp's OpenCL host loop.
+// mipgpu.cpp -- C-ABI engine (include/mipgpu.h): device set-up, buffers, the upload of the
+// planned work lists (work_plan.h) and the per-batch launch sequence that replaces main.cpp's
+// OpenCL host loop.
 #include "mipgpu.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <functional>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -24,8 +24,18 @@
 #include "host_stage_hip.h"
 #include "numa_place.h"
 #include "queue_ring.h"
+#include "work_plan.h"
 
 namespace {
+
+// the planner's geometry (work_plan.h), shared with the public table queries below
+using mipgpu::axis_pos;
+using mipgpu::cu_defined;
+using mipgpu::kMapAltCaller;
+using mipgpu::kMapAltEngine;
+using mipgpu::kMapOrig;
+using mipgpu::kMaps;
+using mipgpu::kShapes;
 
 thread_local std::string g_err;
 
@@ -65,94 +75,7 @@ struct SlowCall {
     if (_e != hipSuccess) return fail("%s: %s", #expr, hipGetErrorString(_e));     \
   } while (0)
 
-const mip_shape_desc kShapes[MIP_NUM_SHAPES] = MIP_SHAPE_TABLE;
 const char *const kShapeNames[MIP_NUM_SHAPES] = MIP_SHAPE_NAMES;
-const uint8_t kW0[16 * 16 * 4] = MIP_WEIGHTS_S0;
-const uint8_t kW1[8 * 16 * 8] = MIP_WEIGHTS_S1;
-const uint8_t kW2[6 * 64 * 7] = MIP_WEIGHTS_S2;
-
-int axis_pos(int base, int step, int dual, int i) {
-  return dual ? base + (i / 2) * step + (i % 2) * dual : base + i * step;
-}
-
-// MIP coefficient tables for the MFMA (layout documented in mip_kernels.h).
-uint16_t to_half(float f) {
-  _Float16 h = (_Float16)f;
-  uint16_t u;
-  memcpy(&u, &h, 2);
-  return u;
-}
-
-std::vector<uint8_t> build_tables() {
-  std::vector<uint8_t> t(mipgpu::kTableBytes, 0);
-  uint16_t *w = reinterpret_cast<uint16_t *>(t.data());
-  float *ctab = reinterpret_cast<float *>(t.data() + mipgpu::kWeightRows * 16);
-  // one matrix row: a0 and w'_1..w'_{nin-1} -> A_j (see mip_kernels.h); returns sum_k A_jk
-  auto put = [&](int row, double a0, const double *wp, int nin) {
-    double sum_w = 0, sum_a = 0;
-    for (int k = 1; k < nin; k++) sum_w += wp[k];
-    double a[8] = {a0 - sum_w, 0, 0, 0, 0, 0, 0, 0};
-    for (int k = 1; k < nin; k++) a[k] = wp[k];
-    for (int k = 0; k < 8; k++) {
-      w[row * 8 + k] = to_half((float)a[k]);
-      sum_a += a[k];
-    }
-    return sum_a;
-  };
-  // sizeId 2: inputs 1..7 use matrix columns 0..6 (p_0 == 0, mip_matrix.cl:441, intra.cl:459-463)
-  for (int m = 0; m < 6; m++)
-    for (int j = 0; j < 64; j++) {
-      double wp[8] = {0};
-      for (int k = 1; k < 8; k++) wp[k] = (kW2[(m * 64 + j) * 7 + k - 1] - 32) / 64.0;
-      const double sa = put(m * 64 + j, 1.0, wp, 8);
-      (void)sa;  // == 1: C' is the constant kAccInitS2
-    }
-  auto small = [&](int base, int modes, int nin, const uint8_t *src) {
-    for (int m = 0; m < modes; m++)
-      for (int j = 0; j < 16; j++) {
-        const uint8_t *wr = src + (m * 16 + j) * nin;
-        double wp[8] = {0};
-        for (int k = 1; k < nin; k++) wp[k] = (wr[k] - 32) / 64.0;
-        const double sa = put(base + m * 16 + j, (96 - wr[0]) / 64.0, wp, nin);
-        ctab[base - mipgpu::kWeightRowOffS1 + m * 16 + j] = (float)(8.0 * (wr[0] - 32) + 0.5 - 1024.0 * sa);
-      }
-  };
-  small(mipgpu::kWeightRowOffS1, 8, 8, kW1);
-  small(mipgpu::kWeightRowOffS0, 16, 4, kW0);
-  for (int i = 0; i < 4; i++) ctab[384 + i] = mipgpu::kAccInitS2;
-  return t;
-}
-
-// Per-quadrant work lists.  The CUs of one size class inside quadrant q (several shapes
-// share a class) are split into groups of at most class_slots() CUs; a group and a range
-// of its mode pairs form a wave task.  Tasks are cut so that none exceeds half of a wave's
-// fair share, then assigned longest-first to the least-loaded of the quadrant's `slices`
-// lists (one per workgroup); each list stays in decreasing cost order, and the waves of a
-// workgroup take its tasks dynamically.  Costs are VALU-instruction estimates per lane.
-// MIPGPU_SHAPE_FILTER="i,j,..." (profiling knob) restricts the search to those shapes.
-// Edge CTUs: the reference reads samples by linear index (intra.cl:100, 236, 718), so CUs
-// right of the frame read the next row (defined costs, searched here too) and only two
-// kinds of CU are undefined (MIP_COST_UNAVAILABLE here): CUs below the frame (y + h > H:
-// stale LDS, intra.cl:96-98) and CUs whose bottom-right sample's linear index
-// (y + h - 1) * W + x + w - 1 is past the frame end (in practice: touching the bottom row
-// and reaching past the right edge).  Such CUs get no task.  CTUs with the same set of
-// defined CUs share a *variant* (ctu_variants: usually the interior, the last CTU row and
-// the last CTU); each variant has its own lists and a fill list of the unavailable cost
-// entries (16-byte units inside the CTU's cost block).
-struct WorkLists {
-  std::vector<mipgpu::WaveTask> tasks;
-  std::vector<mipgpu::Job> jobs;
-  std::vector<int> list_begin;   // [variant][quadrant][slice] + 1
-  std::vector<double> list_cost; // [variant][quadrant][slice]: estimated time of the list on one
-                                 // workgroup (VALU instructions per lane, waves share its tasks)
-  std::vector<uint32_t> fill;    // unavailable cost entries, uint4 index inside the CTU block
-  std::vector<int> fill_begin;   // [variant][quadrant] + 1
-  // decisions only: undefined CUs (CU index inside the CTU) per [variant][quadrant], and the
-  // CUs whose mode pairs are cut over several tasks per [variant]
-  std::vector<uint16_t> dfill, split;
-  std::vector<int> dfill_begin, split_begin;
-  int max_split = 0;
-};
 
 // Profiling knobs that give wrong tables by design (MIPGPU_SHAPE_FILTER, MIPGPU_NO_PAIRS) are
 // honoured only by A/B builds made with KNOBS=-DMIPGPU_PROFILING_KNOBS (the option enters the
@@ -165,358 +88,28 @@ constexpr bool kProfilingKnobs = false;
 #endif
 const char *const kWrongResultKnobs[] = {"MIPGPU_SHAPE_FILTER", "MIPGPU_NO_PAIRS"};
 
-bool shape_selected(int s) {
-  if (!kProfilingKnobs) return true;
-  const char *flt = getenv("MIPGPU_SHAPE_FILTER");
-  if (!flt || !*flt) return true;
-  for (const char *p = flt; *p;) {
-    char *end;
-    const long v = strtol(p, &end, 10);
-    if (end == p) break;
-    if (v == s) return true;
-    p = *end ? end + 1 : end;
-  }
-  return false;
-}
-
-// Task size cap = a wave's fair share / cut_factor (MIPGPU_CUT_FACTOR, tuning knob).
-double cut_factor() {
-  const char *e = getenv("MIPGPU_CUT_FACTOR");
-  return e && atof(e) > 0 ? atof(e) : 2.0;
-}
-
-// Wide CUs (32x4, 16x4, 8x4, 32x8, 16x8) searched as their tall transposes (transposed
-// classes, mip_kernels.h); MIPGPU_TRANSPOSE=0 (A/B knob) searches them as they are.
-bool transpose_wide() {
-  const char *e = getenv("MIPGPU_TRANSPOSE");
-  return !(e && *e == '0');
-}
-
-// MIPGPU_NO_PAIRS=1 (profiling knob): tasks keep their prologue but search no mode pair.
-bool no_pairs() {
-  const char *e = getenv("MIPGPU_NO_PAIRS");
-  return kProfilingKnobs && e && *e == '1';
-}
-
-// Estimated VALU instructions per lane for one mode pair of a task of `ncu` CUs.
-// Is the cost of the CU at frame position (x, y) defined (mipgpu.layout.cu_defined,
-// oracle mipo_cu_defined)?
-bool cu_defined(int width, int height, int x, int y, int w, int h) {
-  return y + h <= height && (long long)(y + h - 1) * width + x + w - 1 < (long long)width * height;
-}
-
-// CU inside the CTU (reference order, 0..5379) -> its shape and CTU-relative position
-// (prediction lists name CUs by this index, like the decision lists).
-struct CuGeo {
-  uint8_t shape, x, y;
-};
-const std::vector<CuGeo> &cu_geo_table() {
-  static const std::vector<CuGeo> table = [] {
-    std::vector<CuGeo> t;
-    t.reserve(MIP_CUS_PER_CTU);
-    for (int s = 0; s < MIP_NUM_SHAPES; s++) {
-      const mip_shape_desc &sd = kShapes[s];
-      for (int cu = 0; cu < sd.ncu; cu++)
-        t.push_back(CuGeo{(uint8_t)s, (uint8_t)axis_pos(sd.xb, sd.xs, sd.xd, cu % sd.ncols),
-                          (uint8_t)axis_pos(sd.yb, sd.ys, sd.yd, cu / sd.ncols)});
-    }
-    return t;
-  }();
-  return table;
-}
-
-// Reference samples above 10 bits.  At widths that are not multiples of 128 the reference's
-// separable filters give the last one or two frame columns values up to ~1.7 x 1023: the
-// horizontal pass there sums the wrapped next-row samples while the scale is the frame-edge
-// class (intra.cl:3446-3458, 3771-3788).  The search kernel's arithmetic is sized for 10-bit
-// samples, so with alternative references the CUs that read columns W-2 or W-1 (their top
-// row, left column or padding sample) are left to the exact per-CU kernel (fixup_kernel).
-bool reads_last_columns(int width, int height, int x, int y, int w, int h) {
-  (void)height;
-  auto col_hit = [&](long long li) { const long long c = li % width; return c >= width - 2; };
-  if (y > 0) {
-    for (int i = 0; i < w; i++)
-      if (col_hit((long long)(y - 1) * width + x + i)) return true;
-  } else if (x > 0 && col_hit(x - 1)) {
-    return true;
-  }
-  if (x > 0) {
-    for (int i = 0; i < h; i++)
-      if (col_hit((long long)(y + i) * width + x - 1)) return true;
-  } else if (y > 0 && col_hit((long long)(y - 1) * width)) {
-    return true;
-  }
-  return false;
-}
-
-// Filtered reference samples the reference leaves undefined because the filter reads memory
-// past the frame's end ("poison"; the oracle's mipo_filter_frame_ex models the same and
-// tests/test_gpu_parity.py compares the two).  The reference's filters work on 128x32 tiles
-// (intra.cl:2873-2879) and address the frame by linear index; halo cells are gated by
-// index < W*H (2D intra.cl:2913-2966 / 3103-3189 and float twins; separable 3336-3366,
-// 3606-3688), so only interior cells can read past the end:
-//   2-D and separable 5-tap: rows inside the frame are read (2904-2909, 3595-3598), so only
-//     the last row right of the frame (wrapping past the end) -- at widths that are not
-//     multiples of 128;
-//   separable 3-tap: interior rows are read unguarded (3330-3332), so every row below the
-//     frame (last tile band when H % 32 != 0) too.
-// An output depends on the cells of its window (2-D: (2R+1)^2; separable: horizontal taps of
-// the vertical taps' rows, 3377-3478 / 3705-3788).  Tiles store all their 128 columns by
-// linear index (3027-3038, 3489-3505): the last tile column's columns right of the frame land
-// on the next row, so their poison counts there too (where the two stores race with defined
-// values, the engine keeps the owning tile's value: one of the reference's outcomes).
-// Only the last tile band (rows [y0, H)) holds such cells; returned as a mask over it.
-struct Poison {
-  int y0 = 0;                  // first frame row of the mask
-  std::vector<uint8_t> mask;   // [(H - y0) * W]: 1 = undefined (linear index - y0 * W)
-  bool any = false;
-  bool at(long long li, int width) const {
-    const long long o = li - (long long)y0 * width;
-    return o >= 0 && o < (long long)mask.size() && mask[(size_t)o];
-  }
-};
-
-Poison filter_poison(int width, int height, int filter) {
-  Poison ps;
-  if (filter < 0) return ps;
-  const bool sep = filter == MIP_FILTER_1D_INT || filter == MIP_FILTER_1D_FLOAT || filter == MIP_FILTER_1D_INT_5x5 ||
-                   filter == MIP_FILTER_1D_FLOAT_5x5;
-  const bool five = filter >= MIP_FILTER_1D_INT_5x5;
-  const long long W = width, H = height, WH = W * H;
-  ps.y0 = 32 * ((height - 1) / 32);
-  ps.mask.assign((size_t)(H - ps.y0) * W, 0);
-  const int qy = ps.y0, rows = std::min(32, height - qy);
-  // cell poison of tile rows ty (interior 0..31) at tile column tc (0..127)
-  auto cell = [&](int qx, int ty, int tc) -> bool {
-    if (ty < 0 || ty >= 32 || tc < 0 || tc >= 128) return false;  // halo: gated, never poison
-    const long long y = qy + ty;
-    if (!(sep && !five) && y >= H) return false;  // 2-D / 5-tap separable: rows below not read
-    return y * W + qx + tc >= WH;
-  };
-  const int R = five ? 2 : 1;
-  for (int qx = 0; qx < width; qx += 128) {
-    uint8_t out[32][128] = {};
-    bool tile_any = false;
-    for (int r = 0; r < rows; r++)
-      for (int c = 0; c < 128; c++) {
-        bool p = false;
-        if (!sep) {
-          for (int dy = -R; dy <= R && !p; dy++)
-            for (int dx = -R; dx <= R && !p; dx++) p = cell(qx, r + dy, c + dx);
-        } else {
-          // vertical taps over rows r-R..r+R (5-tap: only rows with a horizontal pass,
-          // i.e. frame rows, intra.cl:3705-3726), horizontal taps c-R..c+R of each
-          for (int dy = -R; dy <= R && !p; dy++) {
-            if (five && (qy + r + dy < 0 || qy + r + dy >= height)) continue;
-            for (int dx = -R; dx <= R && !p; dx++) p = cell(qx, r + dy, c + dx);
-          }
-        }
-        out[r][c] = p;
-        tile_any |= p;
-      }
-    if (!tile_any) continue;
-    for (int r = 0; r < rows; r++)
-      for (int c = 0; c < 128; c++) {
-        const long long li = (long long)(qy + r) * W + qx + c;  // owning or wrapped store
-        if (out[r][c] && li < WH) {
-          ps.mask[(size_t)(li - (long long)qy * W)] = 1;
-          ps.any = true;
-        }
-      }
-  }
-  return ps;
-}
-
-// Does the CU at frame position (x, y) read a poisoned reference sample (its top row or the
-// top-edge padding sample, its left column or the left-edge padding sample, by linear index
-// as the reference's initBoundaries does, intra.cl:96-107, 232-243)?
-bool reads_poison(const Poison &ps, int width, int x, int y, int w, int h) {
-  if (!ps.any) return false;
-  if (y > 0) {
-    for (int i = 0; i < w; i++)
-      if (ps.at((long long)(y - 1) * width + x + i, width)) return true;
-  } else if (x > 0 && ps.at(x - 1, width)) {
-    return true;
-  }
-  if (x > 0) {
-    for (int i = 0; i < h; i++)
-      if (ps.at((long long)(y + i) * width + x - 1, width)) return true;
-  } else if (y > 0 && ps.at((long long)(y - 1) * width, width)) {
-    return true;
-  }
-  return false;
-}
-
-// CTU -> variant = index of the CTU's set of CUs the search kernel computes (the others get
-// MIP_COST_UNAVAILABLE from the fill lists; the fixup kernel overwrites its CUs after).
-// Three maps share the variants (kMapOrig / kMapAltCaller / kMapAltEngine): original
-// references (every defined CU); caller-supplied alternative references (minus the fixup CUs
-// when the width is not a multiple of 128); the engine filter's references (minus the fixup
-// CUs and minus the CUs that read a sample the reference's filter leaves undefined,
-// filter_poison -- those are MIP_COST_UNAVAILABLE).
-constexpr int kMapOrig = 0, kMapAltCaller = 1, kMapAltEngine = 2, kMaps = 3;
-struct CtuVariants {
-  std::vector<uint8_t> of_ctu[kMaps];
-  std::vector<std::vector<bool>> pattern;         // [variant][CU in CTU order]
-  std::vector<mipgpu::FixupCu> fixup[kMaps];      // ALT: CUs computed by the fixup kernel
-};
-
-CtuVariants ctu_variants(int width, int height, int filter) {
-  CtuVariants v;
-  const int cols = (width + 127) / 128, n = cols * ((height + 127) / 128);
-  const Poison ps = filter_poison(width, height, filter);
-  for (int map = 0; map < kMaps; map++)
-    for (int c = 0; c < n; c++) {
-      const int cx = 128 * (c % cols), cy = 128 * (c / cols);
-      // only CTUs whose CUs reach the last columns can hold fixup CUs (wraps: W < 256)
-      const bool near_edge = map != kMapOrig && width % 128 && (cx + 256 >= width || width < 256);
-      // only CTUs whose CUs reach the poisoned band (one CTU row up: left columns wrap)
-      const bool near_poison = map == kMapAltEngine && ps.any && cy + 256 > ps.y0;
-      std::vector<bool> pat;
-      pat.reserve(MIP_CUS_PER_CTU);
-      int k = 0;
-      for (int s = 0; s < MIP_NUM_SHAPES; s++) {
-        const mip_shape_desc &sd = kShapes[s];
-        for (int cu = 0; cu < sd.ncu; cu++, k++) {
-          const int lx = axis_pos(sd.xb, sd.xs, sd.xd, cu % sd.ncols), ly = axis_pos(sd.yb, sd.ys, sd.yd, cu / sd.ncols);
-          bool on = cu_defined(width, height, cx + lx, cy + ly, sd.w, sd.h);
-          if (on && near_poison && reads_poison(ps, width, cx + lx, cy + ly, sd.w, sd.h)) on = false;
-          if (on && near_edge && reads_last_columns(width, height, cx + lx, cy + ly, sd.w, sd.h)) {
-            on = false;
-            v.fixup[map].push_back(mipgpu::FixupCu{(uint32_t)c, (uint16_t)k, (uint8_t)s, 0});
-          }
-          pat.push_back(on);
-        }
-      }
-      size_t var = 0;
-      while (var < v.pattern.size() && v.pattern[var] != pat) var++;
-      if (var == v.pattern.size()) v.pattern.push_back(pat);
-      v.of_ctu[map].push_back((uint8_t)std::min<size_t>(var, 255));
-    }
-  return v;
-}
-
-double pair_cost(int cls, int ncu) {
-  const int w = mipgpu::kClassW[cls], h = mipgpu::kClassH[cls];
-  const int sid = mipgpu::class_size_id(w, h), v = mipgpu::kClassV[cls];
-  const int nout = sid == 2 ? 64 : 16;
-  const double blocks = (double)h / 4 / v;
-  const double mfma = ((ncu + 7) / 8) * (nout / 16);
-  return blocks * 200.0 + mfma * 12.0 + 40.0;
-}
-
-WorkLists build_work(int slices, int waves, int width, int height, const CtuVariants &cv) {
-  WorkLists wl;
-  const int cols = (width + 127) / 128;
-  (void)cols;
-  for (int vq = 0; vq < 4 * (int)cv.pattern.size(); vq++) {
-    const int var = vq / 4, q = vq % 4;
-    wl.fill_begin.push_back((int)wl.fill.size());
-    wl.dfill_begin.push_back((int)wl.dfill.size());
-    if (q == 0) {
-      if (var > 0) wl.max_split = std::max(wl.max_split, (int)wl.split.size() - wl.split_begin.back());
-      wl.split_begin.push_back((int)wl.split.size());
-    }
-    struct Piece { mipgpu::WaveTask t; double cost; };
-    std::vector<Piece> pieces;
-    std::vector<std::vector<mipgpu::Job>> cls_cus(mipgpu::kNumClasses);
-    int shape_cu0 = 0;  // first CU of the shape inside the CTU (reference order)
-    for (int s = 0; s < MIP_NUM_SHAPES; shape_cu0 += kShapes[s].ncu, s++) {
-      if (!shape_selected(s)) continue;
-      const mip_shape_desc &sd = kShapes[s];
-      int cls = mipgpu::size_class(sd.w, sd.h);
-      if (transpose_wide() && mipgpu::kClassTransposed[cls] >= 0) cls = mipgpu::kClassTransposed[cls];
-      for (int cu = 0; cu < sd.ncu; cu++) {
-        const int x = axis_pos(sd.xb, sd.xs, sd.xd, cu % sd.ncols), y = axis_pos(sd.yb, sd.ys, sd.yd, cu / sd.ncols);
-        if (x / 64 != (q & 1) || y / 64 != (q >> 1)) continue;
-        if (!cv.pattern[var][shape_cu0 + cu]) {
-          const uint32_t off = sd.cost_offset + cu * 2 * sd.modes;  // multiple of 4 entries
-          for (uint32_t u = 0; u < (uint32_t)(2 * sd.modes) / 4; u++) wl.fill.push_back(off / 4 + u);
-          wl.dfill.push_back((uint16_t)(shape_cu0 + cu));
-          continue;
-        }
-        cls_cus[cls].push_back(mipgpu::Job{(uint32_t)(sd.cost_offset + cu * 2 * sd.modes), (uint8_t)(x % 64),
-                                           (uint8_t)(y % 64), (uint16_t)(shape_cu0 + cu)});
-      }
-    }
-    double total = 0;
-    for (int cls = 0; cls < mipgpu::kNumClasses; cls++) {
-      const std::vector<mipgpu::Job> &v = cls_cus[cls];
-      if (v.empty()) continue;
-      const int nv = (int)v.size(), slots = mipgpu::class_slots(cls);
-      const int sid = mipgpu::class_size_id(mipgpu::kClassW[cls], mipgpu::kClassH[cls]);
-      const int modes = sid == 2 ? 6 : (sid == 1 ? 8 : 16);
-      // groups (class, CUs): full tasks plus a remainder task of the class's row-part variant
-      // when the remainder fits it; otherwise equal-sized groups
-      // (variant tasks replace one base task when they occupy fewer lane-blocks: a task of
-      // V row parts gives every lane H / (4 V) blocks per mode pair)
-      std::vector<std::pair<int, int>> groups;
-      const int var = mipgpu::kClassVariant[cls], rem = nv % slots;
-      const int nvar = var >= 0 ? (rem + mipgpu::class_slots(var) - 1) / mipgpu::class_slots(var) : 0;
-      if (rem > 0 && var >= 0 && nvar * mipgpu::kClassV[cls] < mipgpu::kClassV[var]) {
-        for (int g = 0; g < nv / slots; g++) groups.push_back({cls, slots});
-        for (int g = 0, at = 0; g < nvar; g++) {
-          const int n = (rem - at) / (nvar - g);
-          groups.push_back({var, n});
-          at += n;
-        }
-      } else {
-        const int ng = (nv + slots - 1) / slots;
-        for (int g = 0, at = 0; g < ng; g++) {
-          const int n = (nv - at) / (ng - g);
-          groups.push_back({cls, n});
-          at += n;
-        }
-      }
-      for (int g = 0, at = 0; g < (int)groups.size(); g++) {
-        const int gc = groups[g].first, n = groups[g].second;
-        const uint32_t first = (uint32_t)wl.jobs.size();
-        wl.jobs.insert(wl.jobs.end(), v.begin() + at, v.begin() + at + n);
-        at += n;
-        const double c = pair_cost(gc, n);
-        pieces.push_back({mipgpu::WaveTask{(uint8_t)gc, (uint8_t)n, 0, (uint8_t)modes, first}, c});
-        total += c * modes;
-      }
-    }
-    // cut long tasks into pair ranges
-    const double cap = std::max(1.0, total / (slices * waves) / cut_factor());
-    std::vector<Piece> cut;
-    for (const Piece &p : pieces) {
-      const int np = p.t.q1 - p.t.q0;
-      const int parts = std::max(1, std::min(np, (int)std::ceil(p.cost * np / cap)));
-      if (parts > 1)
-        for (uint32_t j = 0; j < p.t.ncu; j++) wl.split.push_back(wl.jobs[p.t.cu0 + j].cu);
-      for (int i = 0; i < parts; i++) {
-        Piece c = p;
-        c.t.q0 = (uint8_t)(p.t.q0 + np * i / parts);
-        c.t.q1 = (uint8_t)(p.t.q0 + np * (i + 1) / parts);
-        c.cost = p.cost * (c.t.q1 - c.t.q0) + 150.0;
-        if (no_pairs()) c.t.q1 = c.t.q0;  // profiling: task prologues only
-        cut.push_back(c);
-      }
-    }
-    std::stable_sort(cut.begin(), cut.end(), [](const Piece &a, const Piece &b) { return a.cost > b.cost; });
-    const int bins = slices;
-    std::vector<double> load(bins, 0.0);
-    std::vector<std::vector<mipgpu::WaveTask>> lists(bins);
-    for (const Piece &p : cut) {
-      const int b = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-      load[b] += p.cost;
-      lists[b].push_back(p.t);
-    }
-    for (int b = 0; b < bins; b++) {
-      wl.list_begin.push_back((int)wl.tasks.size());
-      wl.tasks.insert(wl.tasks.end(), lists[b].begin(), lists[b].end());
-      wl.list_cost.push_back(load[b] / waves);
+// The planner's knobs (work_plan.h PlanKnobs), read once per engine (mip_engine_create):
+//   MIPGPU_CUT_FACTOR (tuning knob): task size cap = a wave's fair share / factor;
+//   MIPGPU_TRANSPOSE=0 (A/B knob): wide CUs are searched as they are;
+//   MIPGPU_SHAPE_FILTER="i,j,..." (profiling knob): the search is restricted to those shapes;
+//   MIPGPU_NO_PAIRS=1 (profiling knob): tasks keep their prologue but search no mode pair.
+mipgpu::PlanKnobs plan_knobs_from_env() {
+  mipgpu::PlanKnobs k;
+  if (const char *e = getenv("MIPGPU_CUT_FACTOR"); e && atof(e) > 0) k.cut_factor = atof(e);
+  if (const char *e = getenv("MIPGPU_TRANSPOSE")) k.transpose_wide = *e != '0';
+  if (!kProfilingKnobs) return k;
+  if (const char *e = getenv("MIPGPU_NO_PAIRS")) k.no_pairs = *e == '1';
+  if (const char *flt = getenv("MIPGPU_SHAPE_FILTER"); flt && *flt) {
+    k.shapes = 0;
+    for (const char *p = flt; *p;) {
+      char *end;
+      const long v = strtol(p, &end, 10);
+      if (end == p) break;
+      if (v >= 0 && v < MIP_NUM_SHAPES) k.shapes |= 1ull << v;
+      p = *end ? end + 1 : end;
     }
   }
-  wl.list_begin.push_back((int)wl.tasks.size());
-  wl.fill_begin.push_back((int)wl.fill.size());
-  wl.dfill_begin.push_back((int)wl.dfill.size());
-  if (!wl.split_begin.empty())
-    wl.max_split = std::max(wl.max_split, (int)wl.split.size() - wl.split_begin.back());
-  wl.split_begin.push_back((int)wl.split.size());
-  return wl;
+  return k;
 }
 
 bool filter_valid(int f, int k) {
@@ -576,22 +169,19 @@ struct mip_engine {
   uint8_t *d_best = nullptr;
   // Work lists, one set per slice count (workgroups per CTU quadrant): small batches need
   // more, smaller workgroups to fill the chip (see pick_work).
+  // `plan` (work_plan.h) is the host's copy of everything planned; work[i] holds the device
+  // copies of plan.work[i]'s lists.
+  mipgpu::EnginePlan plan;
   struct Work {
-    int slices = 1;
-    bool wide = false;  // lists for one 16-wave workgroup per CU (small launches, pick_work)
+    const mipgpu::WorkPlan *host = nullptr;  // slices, wide, max_split, order_cost, nonempty
     mipgpu::WaveTask *d_tasks = nullptr;
     mipgpu::Job *d_jobs = nullptr;
     int *d_lists = nullptr;
     uint32_t *d_fill = nullptr;
     int *d_fill_begin = nullptr;
-    uint16_t *d_dfill = nullptr, *d_split = nullptr;  // decisions only (WorkLists)
+    uint16_t *d_dfill = nullptr, *d_split = nullptr;  // decisions only (WorkPlan)
     int *d_dfill_begin = nullptr, *d_split_begin = nullptr;
-    int max_split = 0;
-    // Small launches: the frame's items longest first (SearchArgs::order), their estimated
-    // costs in that order (pick_work's makespan model).
-    uint32_t *d_order = nullptr;
-    std::vector<double> order_cost;
-    uint32_t nonempty = 0;  // items of a frame with tasks (original references): the first in d_order
+    uint32_t *d_order = nullptr;  // small launches: the frame's items longest first
   };
   std::vector<Work> work;
   // pick_work's choice per frame count for small launches (index into `work`), [alt][wide]
@@ -706,10 +296,6 @@ namespace {
 // CU count limit of one launch (int32 indices in the decision-list kernel).
 constexpr long long kMaxCus = (1LL << 31) - 256;
 
-// Per-item cost beyond its tasks (window staging, barriers, fills), in the task cost
-// model's units (pair_cost: VALU instructions per lane).
-constexpr double kItemOverhead = 600.0;
-
 // MIPGPU_DEC_INLINE=1 (A/B knob): decisions-only chunks of the host pipeline initialise and
 // unpack their split entries on the search stream (before round 5) instead of the download
 // stream.
@@ -752,71 +338,35 @@ bool lpt_order_enabled() {
   return !(e && *e == '0');
 }
 
-// Makespan of `nframes` frames' items taken longest first (SearchArgs::order) by `groups`
-// persistent workgroups: greedy list scheduling of the queue order.
-double lpt_makespan(const std::vector<double> &order_cost, int nframes, int groups) {
-  std::vector<double> fin(groups, 0.0);  // min-heap of finish times
-  for (double c : order_cost)
-    for (int f = 0; f < nframes; f++) {
-      std::pop_heap(fin.begin(), fin.end(), std::greater<double>());
-      fin.back() += c;
-      std::push_heap(fin.begin(), fin.end(), std::greater<double>());
-    }
-  return *std::max_element(fin.begin(), fin.end());
-}
-
 // Small launches on 16-wave workgroups, one per CU (MIPGPU_WIDE: 0 = never, 1 = every small
-// launch; default: below kWideItemsPerGroup items per CU at one slice).  Two 8-wave workgroups (round 4)
-// on a CU progress at very different rates when both run an item (the SIMD arbiter serves the
-// older waves first: 98 vs 170 us for the two items of a CU in a 1080p frame,
-// profiles/r04_item_timeline_1frame.csv), so a launch of ~2 items per CU ends with one
-// workgroup running alone; a 16-wave workgroup has all its waves on one item's tasks.
-// Measured (profiles/r04_small_batch_wide.jsonl): 1 frame 0.185 -> 0.175 ms, 2 frames
-// 0.293 -> 0.314 ms (without a second workgroup the item tails and window stagings idle the
-// CU), 8-16 frames -9 %.
-// Round 6 (six-wave 12-wave workgroups, tools/experiments/r06/small_ab.sh): 2-frame launches
-// (3.98 items per CU) 0.2905 ms on 12-wave workgroups vs 0.2967 wide, 1 frame 0.1758 vs 0.1743
-// -- the threshold moved from 4 to 3 items per CU (only one-frame 1080p launches go wide).
-constexpr int kWideItemsPerGroup = 3;
+// launch; default: work_plan.h few_items_per_cu).
 bool wide_launch(long long items1, int cus) {
   if (cus < 1) return false;  // no 16-wave workgroup fits a CU of this device
   const char *e = getenv("MIPGPU_WIDE");
   if (e && *e == '0') return false;
   if (e && *e == '1') return true;
-  return items1 < (long long)kWideItemsPerGroup * cus;
+  return mipgpu::few_items_per_cu(items1, cus);
 }
 
 // Work lists for a launch of `nframes`: items (quadrant x slice) for the persistent grid.
 // Large launches (>= kPrefetchMinItems items per workgroup at one slice): one slice.
 // Small ones take their items longest first, on 8- or 16-wave workgroups (wide_launch); the
-// slice count is the one whose predicted makespan (lpt_makespan, per frame count, cached) is
-// the shortest.  (Before the LPT order: 1 frame -> 2 slices 5076 frames/s at 1080p (1: 4842,
-// 4: 4770).)
+// slice count is the one whose predicted makespan (work_plan.h shortest_makespan, per frame
+// count, cached) is the shortest.  (Before the LPT order: 1 frame -> 2 slices 5076 frames/s
+// at 1080p (1: 4842, 4: 4770).)
 const mip_engine::Work &pick_work(mip_engine *e, int nframes, int nrange, bool alt) {
   const int groups = e->resident[alt ? 1 : 0];
   const long long items1 = 4LL * nrange * nframes;  // items at one slice
-  if (nrange != e->nctus || items1 >= (long long)mipgpu::kPrefetchMinItems * groups || !lpt_order_enabled()) {
-    const int want = items1 < 1000 && nrange != e->nctus ? 2 : 1;
-    const mip_engine::Work *best = nullptr;
-    for (const mip_engine::Work &w : e->work)
-      if (!w.wide && (!best || std::abs(w.slices - want) < std::abs(best->slices - want))) best = &w;
-    return *best;
-  }
+  if (nrange != e->nctus || items1 >= (long long)mipgpu::kPrefetchMinItems * groups || !lpt_order_enabled())
+    return e->work[mipgpu::closest_slices(e->plan.work, items1 < 1000 && nrange != e->nctus ? 2 : 1)];
   const bool wide = wide_launch(items1, e->resident_wide[alt ? 1 : 0]);
   std::vector<int> &cache = e->small_choice[alt ? 1 : 0][wide ? 1 : 0];
   if ((int)cache.size() <= nframes) cache.resize(nframes + 1, -1);
   int &ch = cache[nframes];
-  if (ch < 0) {
-    const int g = wide ? e->resident_wide[alt ? 1 : 0] : groups;
-    double best = 0;
-    for (size_t i = 0; i < e->work.size(); i++) {
-      if (e->work[i].wide != wide) continue;
-      const double m = lpt_makespan(e->work[i].order_cost, nframes, g);
-      if (ch < 0 || m < best) ch = (int)i, best = m;
-    }
-  }
+  if (ch < 0) ch = mipgpu::shortest_makespan(e->plan.work, wide, nframes, wide ? e->resident_wide[alt ? 1 : 0] : groups);
   return e->work[ch];
 }
+
 }  // namespace
 
 // Samples above 10 bits seen by a search launched before this point (the kernels mark
@@ -958,6 +508,16 @@ void dev_free(void *p) {
   }
   (void)hipFree(p);
 }
+
+// One planned array (work_plan.h) on the device: a block from dev_malloc -- at least one
+// element, so that no list pointer is null -- holding a copy of `v`.
+template <class T>
+int upload(int device, T *&d, const std::vector<T> &v, const char *what) {
+  const size_t bytes = v.size() * sizeof(T);
+  hipError_t err = dev_malloc(device, (void **)&d, std::max(bytes, sizeof(T)));
+  if (err == hipSuccess && bytes) err = hipMemcpy(d, v.data(), bytes, hipMemcpyHostToDevice);
+  return err == hipSuccess ? 0 : fail("uploading %s (%zu bytes) failed: %s", what, bytes, hipGetErrorString(err));
+}
 }  // namespace
 
 // NUMA placement of a device (numa_place.h; none when the bus id or its node is unknown).
@@ -1011,7 +571,7 @@ int mip_shape_info(int shape, int *w, int *h, int *modes, int *ncu, int *cost_of
 int mip_unavailable_cus(int width, int height, int filter, uint8_t *cu_out) {
   if (!cu_out || width <= 0 || height <= 0 || width % 4 || height % 4) return fail("bad unavailable-CU arguments");
   if (filter < MIP_FILTER_NONE || filter > MIP_FILTER_2D_FLOAT_5x5) return fail("invalid filter %d", filter);
-  const Poison ps = filter_poison(width, height, filter);
+  const mipgpu::Poison ps = mipgpu::filter_poison(width, height, filter);
   const int cols = (width + 127) / 128, n = mip_num_ctus(width, height);
   size_t k = 0;
   for (int c = 0; c < n; c++) {
@@ -1020,7 +580,7 @@ int mip_unavailable_cus(int width, int height, int filter, uint8_t *cu_out) {
       const mip_shape_desc &sd = kShapes[s];
       for (int cu = 0; cu < sd.ncu; cu++, k++) {
         const int x = cx + axis_pos(sd.xb, sd.xs, sd.xd, cu % sd.ncols), y = cy + axis_pos(sd.yb, sd.ys, sd.yd, cu / sd.ncols);
-        cu_out[k] = !cu_defined(width, height, x, y, sd.w, sd.h) || reads_poison(ps, width, x, y, sd.w, sd.h);
+        cu_out[k] = !cu_defined(width, height, x, y, sd.w, sd.h) || mipgpu::reads_poison(ps, width, x, y, sd.w, sd.h);
       }
     }
   }
@@ -1239,94 +799,39 @@ int mip_engine_create(int device, int width, int height, const mip_opts *opts, m
   ALLOC(e->d_best_cost, ncu * o.best_k * 4);
   ALLOC(e->d_split_acc, ncu * 4);
   if (hipMemset(e->d_split_acc, 0xff, ncu * 4) != hipSuccess) return cleanup(fail("hipMemset failed"));
-  const CtuVariants cv = ctu_variants(width, height, o.filter);
+#undef ALLOC
+  // What the search computes (work_plan.h), planned once; the device blocks are taken in a
+  // fixed order (the block cache hands out blocks by size).
+  e->plan = mipgpu::plan_engine(width, height, o.filter,
+                                o.slices_per_ctu > 0 ? std::vector<int>{o.slices_per_ctu} : std::vector<int>{1, 2, 4},
+                                plan_knobs_from_env());
+  const mipgpu::CtuVariants &cv = e->plan.cv;
   if (cv.pattern.size() > (size_t)mipgpu::kMaxCtuVariants)
     return cleanup(fail("too many CTU variants (%zu)", cv.pattern.size()));
   for (int m = 0; m < kMaps; m++) {
-    ALLOC(e->d_ctu_var[m], cv.of_ctu[m].size());
-    if (hipMemcpy(e->d_ctu_var[m], cv.of_ctu[m].data(), cv.of_ctu[m].size(), hipMemcpyHostToDevice) != hipSuccess)
-      return cleanup(fail("uploading CTU variants failed"));
+    if (upload(device, e->d_ctu_var[m], cv.of_ctu[m], "CTU variants") != 0) return cleanup(-1);
     e->nfixup[m] = (int)cv.fixup[m].size();
-    if (e->nfixup[m]) {
-      ALLOC(e->d_fixup[m], cv.fixup[m].size() * sizeof(mipgpu::FixupCu));
-      if (hipMemcpy(e->d_fixup[m], cv.fixup[m].data(), cv.fixup[m].size() * sizeof(mipgpu::FixupCu),
-                    hipMemcpyHostToDevice) != hipSuccess)
-        return cleanup(fail("uploading fixup CUs failed"));
-    }
+    if (e->nfixup[m] && upload(device, e->d_fixup[m], cv.fixup[m], "fixup CUs") != 0) return cleanup(-1);
   }
-  std::vector<int> slice_set;
-  if (o.slices_per_ctu > 0) slice_set = {o.slices_per_ctu};
-  else slice_set = {1, 2, 4};
-  std::vector<std::pair<int, bool>> work_set;  // (slices, wide)
-  for (int wide = 0; wide < 2; wide++)
-    for (int sl : slice_set) work_set.push_back({sl, wide != 0});
-  for (const auto &[sl, wide] : work_set) {
-    const WorkLists wl = build_work(sl, wide ? mipgpu::kWideWaves : mipgpu::kSearchWaves, width, height, cv);
-    mip_engine::Work w;
-    w.slices = sl;
-    w.wide = wide;
-    e->work.push_back(w);
+  for (const mipgpu::WorkPlan &wp : e->plan.work) {
+    e->work.emplace_back();
     mip_engine::Work &ew = e->work.back();
-    ALLOC(ew.d_tasks, std::max<size_t>(1, wl.tasks.size()) * sizeof(mipgpu::WaveTask));
-    ALLOC(ew.d_jobs, std::max<size_t>(1, wl.jobs.size()) * sizeof(mipgpu::Job));
-    ALLOC(ew.d_lists, wl.list_begin.size() * sizeof(int));
-    ALLOC(ew.d_fill, std::max<size_t>(1, wl.fill.size()) * sizeof(uint32_t));
-    ALLOC(ew.d_fill_begin, wl.fill_begin.size() * sizeof(int));
-    if ((!wl.fill.empty() &&
-         hipMemcpy(ew.d_fill, wl.fill.data(), wl.fill.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) ||
-        hipMemcpy(ew.d_fill_begin, wl.fill_begin.data(), wl.fill_begin.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
-      return cleanup(fail("uploading fill lists failed"));
-    if ((!wl.tasks.empty() &&
-         (hipMemcpy(ew.d_tasks, wl.tasks.data(), wl.tasks.size() * sizeof(mipgpu::WaveTask), hipMemcpyHostToDevice) != hipSuccess ||
-          hipMemcpy(ew.d_jobs, wl.jobs.data(), wl.jobs.size() * sizeof(mipgpu::Job), hipMemcpyHostToDevice) != hipSuccess)) ||
-        hipMemcpy(ew.d_lists, wl.list_begin.data(), wl.list_begin.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
-      return cleanup(fail("uploading work lists failed"));
-    ew.max_split = wl.max_split;
-    {  // small launches: the frame's items longest first (original-reference lists' costs)
-      const int per_ctu = 4 * sl;
-      std::vector<double> cost((size_t)e->nctus * per_ctu);
-      for (int c = 0; c < e->nctus; c++)
-        for (int g = 0; g < per_ctu; g++) {
-          const int q = g / sl, slc = g % sl, l = (cv.of_ctu[kMapOrig][c] * 4 + q) * sl + slc;
-          const bool empty = wl.list_begin[l + 1] == wl.list_begin[l];
-          cost[(size_t)c * per_ctu + g] = wl.list_cost[l] + (empty ? kItemOverhead / 8 : kItemOverhead);
-        }
-      std::vector<uint32_t> order(cost.size());
-      for (size_t i = 0; i < order.size(); i++) order[i] = (uint32_t)i;
-      std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cost[a] > cost[b]; });
-      ew.order_cost.resize(order.size());
-      for (size_t i = 0; i < order.size(); i++) ew.order_cost[i] = cost[order[i]];
-      for (uint32_t it : order) {  // (the empty items cost kItemOverhead / 8: they come last)
-        const int c = (int)(it / per_ctu), g = (int)(it % per_ctu), q = g / sl, slc = g % sl;
-        const int l = (cv.of_ctu[kMapOrig][c] * 4 + q) * sl + slc;
-        if (wl.list_begin[l + 1] == wl.list_begin[l]) break;
-        ew.nonempty++;
-      }
-      ALLOC(ew.d_order, order.size() * sizeof(uint32_t));
-      if (hipMemcpy(ew.d_order, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
-        return cleanup(fail("uploading the item order failed"));
-    }
+    ew.host = &wp;
+    if (upload(device, ew.d_tasks, wp.tasks, "tasks") != 0 || upload(device, ew.d_jobs, wp.jobs, "jobs") != 0 ||
+        upload(device, ew.d_lists, wp.list_begin, "task lists") != 0 || upload(device, ew.d_fill, wp.fill, "fill entries") != 0 ||
+        upload(device, ew.d_fill_begin, wp.fill_begin, "fill lists") != 0 ||
+        upload(device, ew.d_order, wp.order, "the item order") != 0 ||
+        upload(device, ew.d_dfill, wp.dfill, "undefined CUs") != 0 ||
+        upload(device, ew.d_dfill_begin, wp.dfill_begin, "undefined-CU lists") != 0 ||
+        upload(device, ew.d_split, wp.split, "split CUs") != 0 ||
+        upload(device, ew.d_split_begin, wp.split_begin, "split-CU lists") != 0)
+      return cleanup(-1);
     if (getenv("MIPGPU_WORK_STATS"))  // diagnostic: list sizes per slice count
       fprintf(stderr, "mipgpu work %dx%d slices %d: %zu tasks, %zu jobs, %zu fill, %zu undefined CUs, %zu split CUs (max %d per CTU)\n",
-              width, height, sl, wl.tasks.size(), wl.jobs.size(), wl.fill.size(), wl.dfill.size(), wl.split.size(),
-              wl.max_split);
-    ALLOC(ew.d_dfill, std::max<size_t>(1, wl.dfill.size()) * sizeof(uint16_t));
-    ALLOC(ew.d_dfill_begin, wl.dfill_begin.size() * sizeof(int));
-    ALLOC(ew.d_split, std::max<size_t>(1, wl.split.size()) * sizeof(uint16_t));
-    ALLOC(ew.d_split_begin, wl.split_begin.size() * sizeof(int));
-    if ((!wl.dfill.empty() &&
-         hipMemcpy(ew.d_dfill, wl.dfill.data(), wl.dfill.size() * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess) ||
-        (!wl.split.empty() &&
-         hipMemcpy(ew.d_split, wl.split.data(), wl.split.size() * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess) ||
-        hipMemcpy(ew.d_dfill_begin, wl.dfill_begin.data(), wl.dfill_begin.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(ew.d_split_begin, wl.split_begin.data(), wl.split_begin.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
-      return cleanup(fail("uploading decision lists failed"));
+              width, height, wp.slices, wp.tasks.size(), wp.jobs.size(), wp.fill.size(), wp.dfill.size(), wp.split.size(),
+              wp.max_split);
   }
-  const std::vector<uint8_t> tab = build_tables();
-  ALLOC(e->d_tables, tab.size());
-#undef ALLOC
-  if (hipMemcpy(e->d_tables, tab.data(), tab.size(), hipMemcpyHostToDevice) != hipSuccess)
-    return cleanup(fail("uploading static tables failed"));
+  if (upload(device, e->d_tables, mipgpu::build_tables(), "static tables") != 0) return cleanup(-1);
   *out = e;
   return 0;
 }
@@ -1404,7 +909,8 @@ static int search_device_impl(mip_engine *e, const uint16_t *d_frames, const uin
   a.sad = d_sad;
   a.satd = d_satd;
   const mip_engine::Work &work = pick_work(e, nframes, nrange, alt);
-  int resident = work.wide ? e->resident_wide[alt ? 1 : 0] : e->resident[alt ? 1 : 0];
+  const mipgpu::WorkPlan &wp = *work.host;
+  int resident = wp.wide ? e->resident_wide[alt ? 1 : 0] : e->resident[alt ? 1 : 0];
   // Host-pipeline chunks whose searches alternate between the two search streams and are too
   // small to prefetch (round 6).  At six waves per SIMD a full grid of the batched kernel
   // leaves no room on a CU for the next chunk's workgroups nor for the download stream's
@@ -1413,14 +919,14 @@ static int search_device_impl(mip_engine *e, const uint16_t *d_frames, const uin
   // twin (8-wave workgroups, two per CU: the occupancy rounds 1-5 ran the whole pipeline at),
   // or -- MIPGPU_PIPE_KERNEL=6 -- one 12-wave workgroup per CU (8 queued one-frame
   // decisions-only calls 4740 -> 5100 frames/s, 32 calls 5550 -> 6340).
-  const bool pipe_small = alternating && !work.wide &&
-                          (long long)4 * work.slices * nrange * nframes < (long long)mipgpu::kPrefetchMinItems * resident;
+  const bool pipe_small = alternating && !wp.wide &&
+                          (long long)4 * wp.slices * nrange * nframes < (long long)mipgpu::kPrefetchMinItems * resident;
   const int pk = pipe_kernel();
   // (decisions-only pipeline chunks of any size too: their downloads -- blit kernels on torch's
   // runtime -- and split unpacking run beside the next chunk's search; 8 queued 128-frame
   // calls 7097-7121 -> 7191-7247 frames/s, tools/experiments/r06/e2e_twin.sh; full-table
   // chunks are PCIe-bound either way and keep the six-wave kernel)
-  const bool four = ((pk == 4 && (pipe_small || (decisions_only && done))) || (pk == 8 && done)) && !work.wide &&
+  const bool four = ((pk == 4 && (pipe_small || (decisions_only && done))) || (pk == 8 && done)) && !wp.wide &&
                     e->resident_four[alt ? 1 : 0] > 0;
   if (four) resident = e->resident_four[alt ? 1 : 0];
   else if (pipe_small && pk == 6) resident = std::max(1, resident / 2);
@@ -1442,34 +948,32 @@ static int search_device_impl(mip_engine *e, const uint16_t *d_frames, const uin
   a.nctus = e->nctus;
   a.ctu0 = ctu0;
   a.nrange = nrange;
-  a.slices = work.slices;
+  a.slices = wp.slices;
   a.status = d_status;  // the calling API's status set (mip_engine::h_status)
   a.frame_status = frame_status;  // merged chunks: each frame's own call's set
   a.check_refs = alt && caller_refs;
   a.order = lpt_order_enabled() ? work.d_order : nullptr;  // launch_search drops it for large / range launches
   // pair mode of 16-wave launches (original references; launch_search checks the rest)
   const char *pv = getenv("MIPGPU_PAIR");  // A/B knob: 0 = 16-wave launches take items one at a time
-  a.nonempty = work.wide && !alt && a.order && !(pv && *pv == '0') ? work.nonempty * (uint32_t)nframes : 0;
+  a.nonempty = wp.wide && !alt && a.order && !(pv && *pv == '0') ? wp.nonempty * (uint32_t)nframes : 0;
   // MIPGPU_WAVE_TIMING=file (profiling): per-task cycles appended to `file` (synchronous;
   // one binary record of uint64 [workgroup][wave][kClockSlots] per launch), and the task
   // lists to `file`.tasks once.
   static const char *timing = getenv("MIPGPU_WAVE_TIMING");
   std::vector<uint64_t> clocks;
   if (timing) {
-    const size_t n = (size_t)4 * work.slices * nrange * nframes * mipgpu::kClockSlots;
+    const size_t n = (size_t)4 * wp.slices * nrange * nframes * mipgpu::kClockSlots;
     HIP_TRY(hipMalloc((void **)&a.wave_clock, n * 8));
     HIP_TRY(hipMemsetAsync(a.wave_clock, 0, n * 8, s));
     clocks.resize(n);
     static std::atomic<bool> dumped{false};
     if (!dumped.exchange(true)) {
-      const WorkLists wl = build_work(work.slices, work.wide ? mipgpu::kWideWaves : mipgpu::kSearchWaves, e->width, e->height,
-                                      ctu_variants(e->width, e->height, e->opts.filter));
       if (FILE *f = fopen((std::string(timing) + ".tasks").c_str(), "w")) {
-        fprintf(f, "{\"slices\": %d, \"list_begin\": [", work.slices);
-        for (size_t i = 0; i < wl.list_begin.size(); i++) fprintf(f, "%s%d", i ? ", " : "", wl.list_begin[i]);
+        fprintf(f, "{\"slices\": %d, \"list_begin\": [", wp.slices);
+        for (size_t i = 0; i < wp.list_begin.size(); i++) fprintf(f, "%s%d", i ? ", " : "", wp.list_begin[i]);
         fprintf(f, "], \"tasks\": [");
-        for (size_t i = 0; i < wl.tasks.size(); i++)
-          fprintf(f, "%s[%d, %d, %d, %d]", i ? ", " : "", wl.tasks[i].cls, wl.tasks[i].ncu, wl.tasks[i].q0, wl.tasks[i].q1);
+        for (size_t i = 0; i < wp.tasks.size(); i++)
+          fprintf(f, "%s[%d, %d, %d, %d]", i ? ", " : "", wp.tasks[i].cls, wp.tasks[i].ncu, wp.tasks[i].q0, wp.tasks[i].q1);
         fprintf(f, "]}\n");
         fclose(f);
       }
@@ -1481,7 +985,7 @@ static int search_device_impl(mip_engine *e, const uint16_t *d_frames, const uin
   if (decisions_only && split_acc && defer_split) a.split_acc = split_acc;
   else defer_split = nullptr;
   const mipgpu::SplitArgs sa{work.d_split, work.d_split_begin, a.ctu_var, d_best, d_best_cost,
-                             e->nctus, ctu0, nrange, work.max_split, a.split_acc};
+                             e->nctus, ctu0, nrange, wp.max_split, a.split_acc};
   if (defer_split) *defer_split = sa;
   if (decisions_only && !defer_split) HIP_TRY(mipgpu::launch_dec_split(sa, nframes, true, s));
   // the host pipeline's launches (on the engine's search streams) use their own rings
@@ -1498,7 +1002,7 @@ static int search_device_impl(mip_engine *e, const uint16_t *d_frames, const uin
   hipEvent_t stop = done && last ? *done : nullptr;
   mipgpu::SearchLaunchInfo li{};
   const hipError_t le = four ? SLOW_CALL(mipgpu::launch_search_four(a, nframes, alt, resident, false, s, stop, &li))
-                             : SLOW_CALL(mipgpu::launch_search(a, nframes, alt, resident, work.wide, s, stop, &li));
+                             : SLOW_CALL(mipgpu::launch_search(a, nframes, alt, resident, wp.wide, s, stop, &li));
   if (le == hipSuccess && stop) *done = nullptr;
   if (le == hipSuccess) {  // mip_search_census (every caller holds e->mu)
     const int w = li.waves == 12 ? 0 : li.waves == 16 ? 1 : 2;
@@ -2244,7 +1748,7 @@ int mip_pred_layout(int width, int height, int nframes, int layout, mip_pred_ite
   if (width <= 0 || height <= 0 || width % 4 || height % 4 || nframes < 1 || n < 0 || (n && !items) || !out_samples)
     return fail("bad prediction-layout arguments");
   if (layout != MIP_PRED_PACKED && layout != MIP_PRED_FRAME) return fail("unknown prediction layout %d", layout);
-  const std::vector<CuGeo> &geo = cu_geo_table();
+  const std::vector<mipgpu::CuGeo> &geo = mipgpu::cu_geo_table();
   const int cols = (width + 127) / 128, ncus = mip_num_ctus(width, height) * MIP_CUS_PER_CTU;
   const int64_t fs = (int64_t)width * height;
   int64_t next = 0;
@@ -2254,7 +1758,7 @@ int mip_pred_layout(int width, int height, int nframes, int layout, mip_pred_ite
       return fail("prediction item %lld: frame %d outside 0..%d", (long long)i, it.frame, nframes - 1);
     if (it.cu < 0 || it.cu >= ncus) return fail("prediction item %lld: cu %d outside 0..%d", (long long)i, it.cu, ncus - 1);
     const int ctu = it.cu / MIP_CUS_PER_CTU;
-    const CuGeo &g = geo[(size_t)(it.cu % MIP_CUS_PER_CTU)];
+    const mipgpu::CuGeo &g = geo[(size_t)(it.cu % MIP_CUS_PER_CTU)];
     const mip_shape_desc &sd = kShapes[g.shape];
     if (layout == MIP_PRED_PACKED) {
       it.pitch = sd.w;
@@ -2283,7 +1787,7 @@ static int ensure_pred_tables(mip_engine *e) {
     HIP_TRY(dev_malloc(e->device, (void **)&e->d_pred_unavail[m], ncus));
     HIP_TRY(hipMemcpy(e->d_pred_unavail[m], un.data(), ncus, hipMemcpyHostToDevice));
   }
-  const std::vector<CuGeo> &geo = cu_geo_table();
+  const std::vector<mipgpu::CuGeo> &geo = mipgpu::cu_geo_table();
   std::vector<uint32_t> packed(geo.size());
   for (size_t i = 0; i < geo.size(); i++) packed[i] = geo[i].shape | (uint32_t)geo[i].x << 8 | (uint32_t)geo[i].y << 16;
   uint32_t *d = nullptr;
