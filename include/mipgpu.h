@@ -280,6 +280,74 @@ int mip_predict_frames(mip_engine *e, const uint16_t *frames, const uint16_t *re
                        const mip_pred_item *items, int64_t n, uint16_t *out, int64_t out_samples,
                        int64_t *skipped);
 
+/* CTU partition decision (additive to ABI 7; no reference counterpart -- the reference stops at
+ * the cost table): which CUs to use.  The 47 CU shapes are closed under VTM's intra partition
+ * defaults for a 128x128 CTU -- quad-tree splits down to 8x8, binary and ternary splits only
+ * below 64, at most three of them under a quad-tree leaf, minimum side 4 -- which reach exactly
+ * the 5376 CUs of the 46 shapes other than 64x64 (the four 64x64 CUs are the quad-tree nodes one
+ * level up).  mip_partition_device finds, per CTU, the minimum-cost partition over that CU set
+ * from the per-CU best costs.
+ *
+ * Input, per CU of a frame: best_cost, int32 [nframes][nCTUs*5380], the K = 1 list of
+ * mip_search_device / mip_topk_device (MIP_COST_UNAVAILABLE marks unavailable CUs); best_mode
+ * (optional, same shape, uint8); penalty, an optional HOST array of one int32 per shape in
+ * 0 .. 1<<20 (NULL = zeros; anything else is an error before any launch).
+ *
+ * Leaf cost of CU c of shape s: best_cost[c] + penalty[s].  A CU is eligible as a leaf only if
+ * best_cost[c] != MIP_COST_UNAVAILABLE and it lies wholly inside the frame (x + w <= W,
+ * y + h <= H in frame coordinates): CUs right of the frame, whose costs come from wrapped
+ * samples, are never leaves.  The penalty is the caller's rate term, lambda * bits of a leaf of
+ * that shape; with zero penalties the sum of distortions favours small blocks.
+ *
+ * Regions.  A region whose top-left sample is outside the frame (x >= W or y >= H) costs 0 and
+ * has no leaves.  Any other region that is not an eligible CU must split, or is infinite.
+ * Quad-tree nodes are the aligned squares of side 128, 64, 32, 16, 8 reached by quad splits
+ * only: 128 is never a leaf; 64 may be a leaf (the 64x64 CU) or quad-split; a node of side <= 32
+ * is also the root of a binary/ternary subtree at depth 0; a node of side >= 16 may quad-split
+ * into four nodes of half the side.  A binary/ternary state (rectangle, d), d in 0..3, is a leaf
+ * if eligible and, if d < 3, may split into children at depth d + 1:
+ *     BT-H  top and bottom halves           needs h >= 8
+ *     BT-V  left and right halves           needs w >= 8
+ *     TT-H  h/4, h/2, h/4 stacked           needs h >= 16
+ *     TT-V  w/4, w/2, w/4 side by side      needs w >= 16
+ * No quad split happens below a binary/ternary split.  VVC's redundant-split bans (e.g. a
+ * binary split of a ternary split's middle part in the same direction) are NOT modelled.
+ *
+ * The cost of a split is the sum of its children's best costs, infinite if any child is infinite
+ * (infinity is a state of its own, never reached through overflow).  Candidates are taken in
+ * the order leaf, BT-H, BT-V, TT-H, TT-V, QT; a later one replaces the current one only if it
+ * is strictly cheaper.  Sums are int32: for costs the search produces (<= 2*w*h*1023) and
+ * penalties <= 1<<20 a CTU's total is below 1.11e9; larger input costs give an unspecified
+ * result (memory-safe and deterministic).  A CTU whose root is infinite has no partition: its
+ * ctu_cost is MIP_COST_UNAVAILABLE and it has no leaves.
+ *
+ * Outputs (device pointers, each optional, at least one given; asynchronous on `stream`, no
+ * engine needed):
+ *   d_leaf        uint8 [nframes][nCTUs*5380]: 1 where the CU is a leaf of the chosen partition,
+ *                 else 0; every byte is written.
+ *   d_ctu_cost, d_ctu_leaves   int32 [nframes][nCTUs].
+ *   d_items       mip_pred_item [nframes][nCTUs][MIP_PART_MAX_LEAVES] (8-byte aligned; needs
+ *                 d_best_mode): the first ctu_leaves entries of a CTU are its leaves in
+ *                 increasing CU index, {frame, cu = ctu*5380 + k, mode = best_mode[cu], pitch = W,
+ *                 offset = frame*W*H + y*W + x} (MIP_PRED_FRAME); the others are {-1, -1, -1, 0, 0},
+ *                 which mip_predict_device skips and counts.  The whole array is a valid device
+ *                 list: passed to mip_predict_device it gives the predicted frames with no host
+ *                 round trip. */
+#define MIP_PART_MAX_LEAVES 1024   /* 4x4 tiling of a CTU */
+int mip_partition_device(const int32_t *d_best_cost, const uint8_t *d_best_mode, int width, int height,
+                         int nframes, const int32_t *penalty, uint8_t *d_leaf, int32_t *d_ctu_cost,
+                         int32_t *d_ctu_leaves, mip_pred_item *d_items, void *stream);
+
+/* Decisions and partition of host frames, synchronous like mip_predict_frames (it first waits
+ * for every call in flight; an open merged chunk is launched): in chunks of at most max_batch
+ * frames -- upload, filter if the engine has one and no references are given, decisions-only
+ * search, partition, download.  Needs opts.best_k <= 1.  best_mode_out / best_cost_out:
+ * [nframes][nCTUs*5380]; leaf_out, ctu_cost_out, ctu_leaves_out as d_leaf, d_ctu_cost,
+ * d_ctu_leaves above.  Every output is optional, at least one must be given. */
+int mip_partition_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
+                         const int32_t *penalty, uint8_t *best_mode_out, int32_t *best_cost_out,
+                         uint8_t *leaf_out, int32_t *ctu_cost_out, int32_t *ctu_leaves_out);
+
 /* Streaming device-to-device copy of `bytes` (a multiple of 16, 16-byte aligned pointers),
  * asynchronous on `stream`: 16 bytes per lane, four loads in flight per lane -- the HBM copy
  * rate bench.py prices the filter kernel against (no reference counterpart). */

@@ -1,6 +1,6 @@
 // mip_kernels.h -- launch interface between the C-ABI host code (mipgpu.cpp) and the
 // gfx950 kernels (mip_search.hip, mip_decide.hip, mip_filter.hip, mip_fixup.hip,
-// mip_predict.hip).  Not part of the public ABI.
+// mip_predict.hip, mip_partition.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -179,5 +179,20 @@ struct PredictArgs {
   int refs_vec;               // refs is 8-byte aligned: top rows are read 4 samples per load
 };
 hipError_t launch_predict(const PredictArgs &a, hipStream_t s);
+
+// CTU partition decision (partition_kernel, mip_partition.hip): one workgroup per (frame, CTU).
+struct PartitionPenalty {
+  int32_t v[47];              // per shape, 0 .. 1 << 20 (checked by the caller)
+};
+struct PartitionArgs {
+  const int32_t *best_cost;   // [nframes][nctus][5380]
+  const uint8_t *best_mode;   // same shape; needed for items only
+  uint8_t *leaf;              // optional outputs (include/mipgpu.h)
+  int32_t *ctu_cost, *ctu_leaves;
+  mip_pred_item *items;
+  int width, height, ctu_cols, nctus, nframes;
+  PartitionPenalty penalty;
+};
+hipError_t launch_partition(const PartitionArgs &a, hipStream_t s);
 
 }  // namespace mipgpu

@@ -23,6 +23,7 @@
 #include "chunk_plan.h"
 #include "host_stage_hip.h"
 #include "numa_place.h"
+#include "partition_plan.h"
 #include "queue_ring.h"
 #include "work_plan.h"
 
@@ -198,6 +199,10 @@ struct mip_engine {
   // and the CU geometry inside a CTU (PredictArgs::geo).
   uint8_t *d_pred_unavail[2] = {};
   uint32_t *d_pred_geo = nullptr;
+  // Partition decision of host frames (mip_partition_frames), allocated at its first use, for
+  // max_batch frames: the leaf flags, and the CTU costs followed by the CTU leaf counts.
+  uint8_t *d_part_leaf = nullptr;
+  int32_t *d_part_ctu = nullptr;
   int resident[2] = {0, 0};  // persistent search grid (workgroups resident on this device), [alt]
   int resident_wide[2] = {0, 0};  // the same for 16-wave workgroups
   int resident_four[2] = {0, 0};  // the four-wave twin's (8-wave workgroups; 0: not available)
@@ -620,6 +625,8 @@ int mip_engine_destroy(mip_engine *e) {
   if (e->d_pred_unavail[1] != e->d_pred_unavail[0]) dev_free(e->d_pred_unavail[1]);
   dev_free(e->d_pred_unavail[0]);
   dev_free(e->d_pred_geo);
+  dev_free(e->d_part_leaf);
+  dev_free(e->d_part_ctu);
   dev_free(e->d_queue);
   if (e->h_status) (void)hipHostFree(e->h_status);
   if (e->h_frame_status) (void)hipHostFree(e->h_frame_status);
@@ -1944,6 +1951,112 @@ int mip_predict_frames(mip_engine *e, const uint16_t *frames, const uint16_t *re
 #undef PRED_TRY
   e->refs_pending = false;
   if (skipped) *skipped = nskip;
+  return done(0);
+}
+
+// ---------------------------------------------------------------- partition decision
+// The argument rules of both partition entry points (before any launch).
+static int partition_args_ok(int width, int height, int nframes, const int32_t *penalty, bool any_output) {
+  if (width <= 0 || height <= 0 || width % 4 || height % 4 || nframes < 1) return fail("bad partition arguments");
+  if (!any_output) return fail("partition: no output given");
+  if (!mipgpu::part_penalty_ok(penalty))
+    return fail("partition: a shape penalty is outside 0..%d", (int)mipgpu::kPartMaxPenalty);
+  if ((long long)nframes * mip_num_ctus(width, height) * MIP_CUS_PER_CTU > kMaxCus)
+    return fail("%d frames exceed %lld CUs per call", nframes, kMaxCus);
+  return 0;
+}
+
+int mip_partition_device(const int32_t *d_best_cost, const uint8_t *d_best_mode, int width, int height, int nframes,
+                         const int32_t *penalty, uint8_t *d_leaf, int32_t *d_ctu_cost, int32_t *d_ctu_leaves,
+                         mip_pred_item *d_items, void *stream) {
+  if (!d_best_cost) return fail("bad partition arguments: d_best_cost is NULL");
+  if (partition_args_ok(width, height, nframes, penalty, d_leaf || d_ctu_cost || d_ctu_leaves || d_items) != 0) return -1;
+  if (d_items && !d_best_mode) return fail("partition: d_items needs d_best_mode");
+  if (reinterpret_cast<uintptr_t>(d_items) & 7) return fail("partition: d_items must be 8-byte aligned");
+  mipgpu::PartitionArgs a{};
+  a.best_cost = d_best_cost;
+  a.best_mode = d_best_mode;
+  a.leaf = d_leaf;
+  a.ctu_cost = d_ctu_cost;
+  a.ctu_leaves = d_ctu_leaves;
+  a.items = d_items;
+  a.width = width;
+  a.height = height;
+  a.ctu_cols = (width + 127) / 128;
+  a.nctus = mip_num_ctus(width, height);
+  a.nframes = nframes;
+  for (int s = 0; s < MIP_NUM_SHAPES; s++) a.penalty.v[s] = penalty ? penalty[s] : 0;
+  HIP_TRY(mipgpu::launch_partition(a, (hipStream_t)stream));
+  return 0;
+}
+
+int mip_partition_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
+                         const int32_t *penalty, uint8_t *best_mode_out, int32_t *best_cost_out, uint8_t *leaf_out,
+                         int32_t *ctu_cost_out, int32_t *ctu_leaves_out) {
+  if (!e) return fail("engine is NULL");
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (!frames) return fail("bad partition arguments: no frames");
+  if (partition_args_ok(e->width, e->height, nframes, penalty,
+                        best_mode_out || best_cost_out || leaf_out || ctu_cost_out || ctu_leaves_out) != 0)
+    return -1;
+  if (e->opts.best_k != 1) return fail("mip_partition_frames needs best_k <= 1 (got %d)", e->opts.best_k);
+  HIP_TRY(hipSetDevice(e->device));
+  if (flush_open(e) != 0) return -1;
+  if (wait_refs_readers(e) != 0) return -1;
+  // asynchronous host searches still in flight use the engine buffers: let them finish
+  HIP_TRY(hipStreamSynchronize(e->stream2));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream4));
+  HIP_TRY(hipStreamSynchronize(e->stream3));
+  if (check_device_status(e) != 0) return -1;  // (an earlier device-API search's violation)
+  const size_t fs = (size_t)e->width * e->height, ncu = (size_t)e->nctus * MIP_CUS_PER_CTU, mb = (size_t)e->opts.max_batch;
+  // the partition outputs' device buffers, for max_batch frames: allocated at their first use,
+  // released with the engine
+  if (!e->d_part_leaf) HIP_TRY(dev_malloc(e->device, (void **)&e->d_part_leaf, mb * ncu));
+  if (!e->d_part_ctu) HIP_TRY(dev_malloc(e->device, (void **)&e->d_part_ctu, mb * e->nctus * 2 * sizeof(int32_t)));
+  uint16_t *t_refs = nullptr;  // caller references on an engine without a reference buffer
+  auto done = [&](int rc) {
+    dev_free(t_refs);
+    return rc;
+  };
+#define PART_TRY(expr)                                                                     \
+  do {                                                                                     \
+    hipError_t _e = (expr);                                                                \
+    if (_e != hipSuccess) return done(fail("%s: %s", #expr, hipGetErrorString(_e)));       \
+  } while (0)
+  uint16_t *d_refs = nullptr;
+  if (refs_or_null) {
+    d_refs = e->d_refs;
+    if (!d_refs) {
+      PART_TRY(dev_malloc(e->device, (void **)&t_refs, mb * fs * 2));
+      d_refs = t_refs;
+    }
+  }
+  hipStream_t s = e->stream;
+  int32_t *d_ctu_cost = e->d_part_ctu, *d_ctu_leaves = e->d_part_ctu + mb * e->nctus;
+  for (int f0 = 0; f0 < nframes; f0 += e->opts.max_batch) {
+    const size_t nb = (size_t)std::min(e->opts.max_batch, nframes - f0);
+    PART_TRY(hipMemcpyAsync(e->d_frames, frames + f0 * fs, nb * fs * 2, hipMemcpyHostToDevice, s));
+    if (d_refs) PART_TRY(hipMemcpyAsync(d_refs, refs_or_null + f0 * fs, nb * fs * 2, hipMemcpyHostToDevice, s));
+    // (without references the search filters the frames itself when the engine has a filter)
+    if (search_device_impl(e, e->d_frames, d_refs, (int)nb, nullptr, nullptr, nullptr, e->d_best, e->d_best_cost, s,
+                           d_refs != nullptr, device_status(e)) != 0)
+      return done(-1);
+    if (mip_partition_device(e->d_best_cost, e->d_best, e->width, e->height, (int)nb, penalty, e->d_part_leaf, d_ctu_cost,
+                             d_ctu_leaves, nullptr, s) != 0)
+      return done(-1);
+    if (best_mode_out) PART_TRY(hipMemcpyAsync(best_mode_out + f0 * ncu, e->d_best, nb * ncu, hipMemcpyDeviceToHost, s));
+    if (best_cost_out) PART_TRY(hipMemcpyAsync(best_cost_out + f0 * ncu, e->d_best_cost, nb * ncu * 4, hipMemcpyDeviceToHost, s));
+    if (leaf_out) PART_TRY(hipMemcpyAsync(leaf_out + f0 * ncu, e->d_part_leaf, nb * ncu, hipMemcpyDeviceToHost, s));
+    if (ctu_cost_out)
+      PART_TRY(hipMemcpyAsync(ctu_cost_out + (size_t)f0 * e->nctus, d_ctu_cost, nb * e->nctus * 4, hipMemcpyDeviceToHost, s));
+    if (ctu_leaves_out)
+      PART_TRY(hipMemcpyAsync(ctu_leaves_out + (size_t)f0 * e->nctus, d_ctu_leaves, nb * e->nctus * 4, hipMemcpyDeviceToHost, s));
+    PART_TRY(hipStreamSynchronize(s));
+  }
+#undef PART_TRY
+  e->refs_pending = false;
+  if (const uint32_t f = take_status(e, mip_engine::kCallRing)) return done(contract_error(f, "mip_partition_frames"));
   return done(0);
 }
 

@@ -59,6 +59,8 @@ def filter_index(name) -> int:
 PRED_ITEM = np.dtype([("frame", "<i4"), ("cu", "<i4"), ("mode", "<i4"), ("pitch", "<i4"), ("offset", "<i8")])
 PRED_LAYOUTS = {"packed": 0, "frame": 1}   # MIP_PRED_PACKED / MIP_PRED_FRAME
 PRED_NONE = 0xFFFF                         # MIP_PRED_NONE: host output samples no item wrote
+PART_MAX_LEAVES = 1024                     # MIP_PART_MAX_LEAVES: list entries per CTU of partition_device
+PART_MAX_PENALTY = 1 << 20                 # per-shape penalties of the partition decision: 0 .. 1<<20
 
 
 class _Opts(ctypes.Structure):
@@ -140,6 +142,8 @@ def library():
         "mip_pred_layout": (ip, [ip, ip, ip, ip, vp, i64, ctypes.POINTER(i64)]),
         "mip_predict_device": (ip, [vp, vp, vp, ip, vp, i64, vp, i64, vp, vp]),
         "mip_predict_frames": (ip, [vp, vp, vp, ip, vp, i64, vp, i64, ctypes.POINTER(i64)]),
+        "mip_partition_device": (ip, [vp, vp, ip, ip, ip, vp, vp, vp, vp, vp, vp]),
+        "mip_partition_frames": (ip, [vp, vp, vp, ip, vp, vp, vp, vp, vp, vp]),
         "mip_time_search_device": (ctypes.c_double, [vp, vp, vp, ip, vp, ip]),
         "mip_host_stats": (ip, [vp, ctypes.POINTER(ctypes.c_uint64), ip]),
         "mip_search_census": (ip, [vp, ctypes.POINTER(ctypes.c_uint64), ip]),
@@ -457,6 +461,26 @@ class MipEngine:
                                                 ctypes.c_void_p(s.cuda_stream)))
         return out
 
+    # ------------------------------------------------------- partition decision
+    def partition(self, frames, penalty=None, refs=None) -> dict:
+        """Decisions and CTU partition of host frames (mip_partition_frames; needs best_k = 1):
+        dict of numpy arrays 'best_mode' uint8 / 'best_cost' int32 / 'leaf' uint8 [F, nCTUs*5380]
+        and 'ctu_cost' / 'ctu_leaves' int32 [F, nCTUs].  `penalty`: see partition_device."""
+        f = self._frames(frames)
+        r = None if refs is None else self._frames(refs)
+        n = f.shape[0]
+        pen = _penalty(penalty)
+        res = {"best_mode": np.empty((n, self.cus_per_frame), np.uint8),
+               "best_cost": np.empty((n, self.cus_per_frame), np.int32),
+               "leaf": np.empty((n, self.cus_per_frame), np.uint8),
+               "ctu_cost": np.empty((n, self.nctus), np.int32),
+               "ctu_leaves": np.empty((n, self.nctus), np.int32)}
+        with self._lock:
+            _check(library().mip_partition_frames(self._h, _ptr(f), _ptr(r), n, _ptr(pen), _ptr(res["best_mode"]),
+                                                  _ptr(res["best_cost"]), _ptr(res["leaf"]), _ptr(res["ctu_cost"]),
+                                                  _ptr(res["ctu_leaves"])))
+        return res
+
     def time_search_device(self, frames, costs, refs=None, reps=10) -> float:
         with self._lock:
             ms = library().mip_time_search_device(self._h, _ptr(frames), _ptr(refs), frames.shape[0], _ptr(costs),
@@ -528,6 +552,45 @@ def topk_device(costs, width, height, k, modes=None, costs_k=None, stream=None):
     return modes, costs_k
 
 
+def _penalty(penalty):
+    """Per-shape penalties as the int32 [47] host array of the C ABI (None: zeros): a scalar (the
+    same for every shape) or a 47-vector.  The range is checked by the library."""
+    if penalty is None:
+        return None
+    p = np.asarray(penalty)
+    if p.ndim == 0:
+        p = np.full(len(SHAPES), p)
+    if p.shape != (len(SHAPES),):
+        raise MipError("penalty must be a scalar or one value per CU shape (%d)" % len(SHAPES))
+    if np.any(p != np.clip(p, -(1 << 31), (1 << 31) - 1)):
+        raise MipError("penalty does not fit int32")
+    return np.ascontiguousarray(p, dtype=np.int32)
+
+
+def partition_device(best_cost, width, height, penalty=None, best_mode=None, leaf=None, ctu_cost=None, ctu_leaves=None,
+                     items=None, stream=None):
+    """CTU partition decision on device tensors (mip_partition_device, contract in
+    include/mipgpu.h): `best_cost` int32 [F, nCTUs*5380] (the K = 1 list of a search), `penalty` a
+    scalar or 47-vector in 0 .. 1<<20 added per leaf of a shape (the caller's rate term).
+    Outputs, each optional, at least one: `leaf` uint8 [F, nCTUs*5380], `ctu_cost` /
+    `ctu_leaves` int32 [F, nCTUs], `items` uint8 [F, nCTUs, PART_MAX_LEAVES * 24] (PRED_ITEM
+    bytes; needs `best_mode` uint8 [F, nCTUs*5380]) -- a device list for predict_device.
+    Asynchronous on `stream` (default: torch's current stream)."""
+    import torch
+    n = best_cost.shape[0]
+    nct = num_ctus(width, height)
+    want = {"best_cost": (best_cost, n * nct * CUS_PER_CTU * 4), "best_mode": (best_mode, n * nct * CUS_PER_CTU),
+            "leaf": (leaf, n * nct * CUS_PER_CTU), "ctu_cost": (ctu_cost, n * nct * 4), "ctu_leaves": (ctu_leaves, n * nct * 4),
+            "items": (items, n * nct * PART_MAX_LEAVES * PRED_ITEM.itemsize)}
+    for name, (t, nbytes) in want.items():
+        if t is not None and (t.numel() * t.element_size() != nbytes or not t.is_contiguous()):
+            raise MipError(f"partition_device: {name} must be a contiguous tensor of {nbytes} bytes")
+    s = stream if stream is not None else torch.cuda.current_stream(best_cost.device)
+    _check(library().mip_partition_device(_ptr(best_cost), _ptr(best_mode), int(width), int(height), n, _ptr(_penalty(penalty)),
+                                          _ptr(leaf), _ptr(ctu_cost), _ptr(ctu_leaves), _ptr(items),
+                                          ctypes.c_void_p(s.cuda_stream)))
+
+
 def copy_device(src, dst, stream=None):
     """Streaming device copy of tensor `src` into `dst` (mip_copy_device; same byte size)."""
     import torch
@@ -548,6 +611,6 @@ def filter_device(frames_in, frames_out, filter, kernel_idx=0, stream=None):
     return frames_out
 
 
-__all__ = ["PRED_ITEM", "PRED_NONE", "pred_items", "MipEngine", "MipError", "build_id", "source_id", "FILTERS", "FILTER_NONE", "filter_index", "filter_device", "topk_device", "library",
+__all__ = ["PRED_ITEM", "PRED_NONE", "pred_items", "PART_MAX_LEAVES", "PART_MAX_PENALTY", "partition_device", "MipEngine", "MipError", "build_id", "source_id", "FILTERS", "FILTER_NONE", "filter_index", "filter_device", "topk_device", "library",
            "pinned_empty", "unavailable_cus", "numa_node", "bind_thread", "device_cache", "copy_device",
            "layout", "SHAPES", "COSTS_PER_CTU", "CUS_PER_CTU", "UNAVAILABLE", "num_ctus"]
