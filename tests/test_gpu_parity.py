@@ -377,7 +377,7 @@ def test_host_pipeline_four_slots_uneven_chunks(gpu_available, filt, k):
 @pytest.mark.parametrize("filt,k", [(None, 0), ("filterFrame_2d_float_5x5_quarterCtu", 2)])
 def test_host_pipeline_ramped_first_chunks(gpu_available, filt, k):
     """A call into an idle pipeline with max_batch 64 (4 slots of 16 frames) ramps its first
-    chunks up (4, 7, 12 frames, then 14 + 14 + 13: mipgpu.cpp search_frames_chunks), a call
+    chunks up (4, 7, 12 frames, then 14 + 14 + 13: host_policy.h call_chunks), a call
     queued behind it does not; full tables + decisions, then decisions only.  Every frame must
     equal the oracle."""
     w, h, n = 136, 72, 64
@@ -876,7 +876,7 @@ def test_idle_call_chunks_fit_their_slot(gpu_available, max_batch, n):
 @pytest.mark.parametrize("filt,k,pk,gather", [(None, 0, "4", "1"), ("filterFrame_2d_float_5x5_quarterCtu", 2, "4", "1"),
                                               (None, 0, "6", "1"), (None, 0, "0", "0")])
 def test_merged_launches_keep_each_call_its_own(gpu_available, monkeypatch, filt, k, pk, gather):
-    """Merged launches (mipgpu.cpp open chunk, ABI 7): small page-locked calls share one search
+    """Merged launches (host_pipeline.cpp open chunk, ABI 7): small page-locked calls share one search
     launch.  MIPGPU_MERGE=hold makes the grouping deterministic (chunks open even into an idle
     pipeline and are launched only by the other triggers): four decisions-only calls, three
     full-table calls, caller references (1 + 2 frames), then four decisions-only calls of which
@@ -951,6 +951,64 @@ def test_merged_launches_keep_each_call_its_own(gpu_available, monkeypatch, filt
             assert np.array_equal(res["best_cost"][i], bc), (f0, kind, i)
             if kind != "dec":
                 assert np.array_equal(res["cost"][i], oc), (f0, kind, i)
+
+
+# test_host_launch_sequence_is_exact: the nonzero entries of the engine's search census after
+# the script, recorded from the build of commit e387e3c (before launch_chunk served both paths).
+LAUNCH_SEQUENCE_CENSUS = {(8, 0, 0, 0): 2, (8, 0, 1, 0): 3, "ordered": 5}
+
+
+def test_host_launch_sequence_is_exact(gpu_available, monkeypatch):
+    """The host pipeline's launch sequence (host_pipeline.cpp launch_chunk, host_policy.h
+    merge_decision / chunk_frames), pinned exactly: MIPGPU_MERGE=hold on three slots of four
+    frames.  Three page-locked one-frame decisions-only calls open and fill a chunk; a pageable
+    full-table call cannot join it (launch 1: the chunk, launch 2: the call); two page-locked
+    full-table calls open the next chunk, which the first wait launches (3); after all six
+    waits the pipeline is idle, so a four-frame decisions-only call -- a whole slot, not small
+    -- is cut in two (4, 5).  Every output equals the oracle; the counters and the census of
+    kernel instances are exact."""
+    from mipgpu import pinned_empty
+    monkeypatch.setenv("MIPGPU_MERGE", "hold")
+    monkeypatch.setenv("MIPGPU_WIDE", "0")
+    w, h = 264, 136
+    frames = synth_frames(w, h, 10, 0x4A7, 0)
+    pf = pinned_empty(frames.shape, np.uint16)
+    pf[:] = frames
+    nct = layout.num_ctus(w, h)
+
+    def outs(nf, full, pinned=True):
+        alloc = pinned_empty if pinned else np.empty
+        o = {"best_mode": alloc((nf, nct * layout.CUS_PER_CTU), np.uint8),
+             "best_cost": alloc((nf, nct * layout.CUS_PER_CTU), np.int32)}
+        if full:
+            o["cost"] = alloc((nf, nct * layout.COSTS_PER_CTU), np.int32)
+        return o
+    # (first frame, frames, full tables, page-locked)
+    calls = [(0, 1, False, True), (1, 1, False, True), (2, 1, False, True),
+             (3, 1, True, False),
+             (4, 1, True, True), (5, 1, True, True)]
+    last = (6, 4, False, True)
+    with MipEngine(w, h, max_batch=4) as eng:
+        def start(f0, nf, full, pinned):
+            src = pf[f0:f0 + nf] if pinned else frames[f0:f0 + nf].copy()
+            return eng.search_async(src, costs=full, best=True, out=outs(nf, full, pinned))
+        tickets = [start(*c) for c in calls]
+        results = [eng.wait(t) for t in tickets]
+        results.append(eng.wait(start(*last)))
+        stats = eng.host_stats()
+        census = {k: v for k, v in eng.search_census().items() if v}
+    print("host_stats", stats)
+    print("census", census)
+    assert stats == {"calls": 7, "launches": 5, "merged_calls": 5, "merged_launches": 2}, stats
+    assert census == LAUNCH_SEQUENCE_CENSUS, census
+    for (f0, nf, full, _), res in zip(calls + [last], results):
+        for i in range(nf):
+            oc = O.search(frames[f0 + i])
+            bm, bc = layout.best_modes(oc, nct)
+            assert np.array_equal(res["best_mode"][i], bm), (f0, i)
+            assert np.array_equal(res["best_cost"][i], bc), (f0, i)
+            if full:
+                assert np.array_equal(res["cost"][i], oc), (f0, i)
 
 
 def test_merged_launches_1080p_default_policy(gpu_available, monkeypatch):

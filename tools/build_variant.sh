@@ -22,7 +22,11 @@ for src in $srcs; do
 done
 /opt/rocm/bin/hipcc $F -DMIP_SIX_WAVES=0 -DMIP_FOUR_WAVE_TWIN=1 -c -o "$tmp/mip_search_four.o" csrc/mip_search.hip \
   2> >(grep -v "macro redefined\|^ *[0-9]* | \|^ *| \|note: previous definition\|warning generated\|^<command line>" >&2) & pids+=($!)
-/opt/rocm/bin/hipcc $F "-DMIPGPU_BUILD_ID=\"$id\"" -c -o "$tmp/mipgpu.o" csrc/mipgpu.cpp & pids+=($!)
+for src in $(make -s cpp-sources); do  # the host sources, likewise; the build ID goes into mipgpu.o
+  idflag=()
+  [ "$src" = csrc/mipgpu.cpp ] && idflag=("-DMIPGPU_BUILD_ID=\"$id\"")
+  /opt/rocm/bin/hipcc $F "${idflag[@]}" -c -o "$tmp/$(basename "$src" .cpp).o" "$src" & pids+=($!)
+done
 for p in "${pids[@]}"; do wait "$p" || { echo "build_variant: a compile failed" >&2; exit 1; }; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o "$out" "$tmp"/*.o
 echo "built $out ($id)"

@@ -1,4 +1,4 @@
-// chunk_plan.h -- frames per chunk of one host-API call (mipgpu.cpp search_frames_chunks;
+// chunk_plan.h -- frames per chunk of one host-API call (host_policy.h chunk_frames / call_chunks;
 // no HIP dependency, unit-tested by tests/cpp/test_chunk_plan.cpp).
 #pragma once
 #include <algorithm>
@@ -6,7 +6,7 @@
 
 namespace mipgpu {
 
-// Largest chunk of a call before the transfer caps (mipgpu.cpp search_frames_chunks): a
+// Largest chunk of a call before the transfer caps (host_policy.h chunk_frames): a
 // slot's frames (`slot_cap`), or -- for a call into an idle pipeline on a small engine
 // (three slots) -- half the call, so that its own upload, search and download overlap, but
 // never more than a slot holds (a larger chunk would spill into the next slot's region).

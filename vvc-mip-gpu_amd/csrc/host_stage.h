@@ -41,6 +41,12 @@
 
 namespace mipgpu {
 
+// The ring's limits, outside the template: host_policy.h sizes a call's chunks by them.
+constexpr int kRingPieces = 16;
+constexpr int kMaxChunkPieces = kRingPieces - 5;  // a chunk's downloads (BounceRing, below)
+constexpr int kMaxChunkUploadPieces = 4;          // a chunk's uploads
+constexpr size_t kMaxRingPiece = 64u << 20;
+
 // Dev provides: types Err, Stream, Event; static constexpr Err kOk, kNotReady (a transfer
 // before reserve()); and
 //   Err host_alloc(char **p, size_t n, bool numa_user);   void host_free(char *p);
@@ -67,13 +73,11 @@ class BounceRing {
   // flight (one event each).  A chunk's downloads must fit the ring with room for the next
   // chunk's uploads (kMaxChunkPieces pieces of downloads; the wasted tail of a wrap is less
   // than one piece), else enqueueing them would wait on the host for the chunk's own search
-  // and the next upload could not be queued behind it (mipgpu.cpp caps pageable chunks by
-  // footprint()).
-  static constexpr int kRing = 16;
-  static constexpr int kMaxChunkPieces = kRing - 5;
-  static constexpr int kMaxChunkUploadPieces = 4;
+  // and the next upload could not be queued behind it (host_policy.h chunk_frames caps
+  // pageable chunks by footprint()).
+  static constexpr int kRing = kRingPieces;
   static constexpr int kEvents = 64;
-  static constexpr size_t kMaxPiece = 64u << 20;
+  static constexpr size_t kMaxPiece = kMaxRingPiece;
   static constexpr size_t kMinPiece = 1u << 20;
   static constexpr size_t kAlign = 4096;  // default part alignment (MIPGPU_RING_ALIGN: tuning knob)
 

@@ -1,5 +1,5 @@
-// mip_kernels.h -- launch interface between the C-ABI host code (mipgpu.cpp) and the
-// gfx950 kernels (mip_search.hip, mip_decide.hip, mip_filter.hip, mip_fixup.hip,
+// mip_kernels.h -- launch interface between the C-ABI host code (mipgpu.cpp, host_pipeline.cpp)
+// and the gfx950 kernels (mip_search.hip, mip_decide.hip, mip_filter.hip, mip_fixup.hip,
 // mip_predict.hip, mip_partition.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -61,8 +61,8 @@ struct SearchArgs {
   // (check_refs) 1 to status[kStatusRefs].  status is engine-owned page-locked host memory
   // (read by the host after the search; only ever written when the contract is broken).
   uint32_t *status;
-  // Merged host-pipeline chunks (several host-API calls in one launch, mipgpu.cpp
-  // open_chunk): frame f of the launch marks frame_status[f] (its own call's status set)
+  // Merged host-pipeline chunks (several host-API calls in one launch, host_pipeline.cpp
+  // flush_open): frame f of the launch marks frame_status[f] (its own call's status set)
   // instead of status; null otherwise.  Read only when the contract is broken.
   uint32_t *const *frame_status;
   int check_refs;
