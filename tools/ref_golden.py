@@ -89,6 +89,14 @@ CONFIGS = {
     "w1280_orig": (1280, 720, 1, 0, 0x1280, None, 0, False, [9, 59]),
     "w1280_2d_int": (1280, 720, 1, 0, 0x1283, "filterFrame_2d_int_quarterCtu", 0, False, [59]),
     "w1280_1d_float5": (1280, 720, 1, 0, 0x1282, "filterFrame_1d_float_5x5", 2, False, [29]),
+    # width residues the fixtures above do not have (W % 128 = 60, 124, 68: the right half's
+    # 64-wide CUs stick out, the filters' W - 1 gates fall on a tile's last columns) and a frame
+    # narrower than the 68-column quadrant window; the last CTU (the corner, at most 20 rows
+    # high: a short row to commit) is recorded
+    "small_w188_1d_int5": (188, 148, 1, 1, 0x3E0, "filterFrame_1d_int_5x5", 1, False, [3]),
+    "small_w252_2d_float3_k2": (252, 132, 1, 0, 0x3E1, "filterFrame_2d_float_quarterCtu", 2, False, [3]),
+    "small_w196_1d_float": (196, 140, 1, 1, 0x3E2, "filterFrame_1d_float", 3, False, [3]),
+    "small_w60_orig": (60, 136, 1, 0, 0x3E3, None, 0, True, [1]),
     # BASELINE configs[3] geometry: 3840x2160 with original references
     "c4_2160p_orig": (3840, 2160, 1, 0, 0x2161, None, 0, False, [29, 509]),
 }

@@ -109,7 +109,9 @@ __device__ __forceinline__ bool sep_fetch(int qx, int qy, int ty, int tc, int W,
       return b + 32 * W + 128 < WH && qx + 128 < W - 1 && qy + 32 < H - 1;
     }
     if (top || bot) return g > 0 && g < WH;
-    return g > 0 && g < WH && (lft ? qx > 0 : qx + 129 < W - 1);
+    // (the reference gates both sides by "< W - 1", intra.cl:3351: the left one matters only
+    // in a tile of one column, W % 128 == 1)
+    return g > 0 && g < WH && (lft ? qx > 0 && qx < W - 1 : qx + 129 < W - 1);
   }
   if ((top || bot) && (lft || rgt)) {
     const bool vy = top ? qy > 0 : qy + ty < H - 1;   // rows Y+32 / Y+33
