@@ -1,12 +1,14 @@
 // dual_census.hip -- which VALU encodings can gfx950 issue two at a time?  One kernel per
 // instruction form (probe_<id>), each wave running 8 independent chains of it; run under
-//   rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU2 GRBM_GUI_ACTIVE -- /tmp/dc [waves/SIMD]
+//   rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU2 GRBM_GUI_ACTIVE -- /tmp/dc [waves/SIMD [id,id,...]]
 // and read VALU instructions per SIMD quad-cycle and the dual-issued share per kernel.
 //   hipcc --offload-arch=gfx950 -O3 tools/dual_census.hip -o /tmp/dc
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <string>
 #include <vector>
 
 #define CHECK(x)                                                                \
@@ -96,6 +98,9 @@ PROBE(fmac_f32, "v_fmac_f32 %0, %1, %2")
 PROBE(add_f16, "v_add_f16 %0, %0, %1")
 PROBE(cvt_f32_u32, "v_cvt_f32_u32 %0, %0")
 PROBE(cvt_u32_f32, "v_cvt_u32_f32 %0, %0")
+PROBE(cvt_pknorm_u16_f32, "v_cvt_pknorm_u16_f32 %0, %0, %1")
+PROBE(pk_lshrrev_b16, "v_pk_lshrrev_b16 %0, 6, %0")
+PROBE(pk_min_u16, "v_pk_min_u16 %0, %0, %1")
 PROBE(add_co_u32, "v_add_co_u32 %0, vcc, %0, %1")
 PROBE(cndmask, "v_cndmask_b32 %0, %0, %1, vcc")
 PROBE(add_u32_e64, "v_add_u32_e64 %0, %0, %1")
@@ -128,6 +133,8 @@ int main(int argc, char **argv) {
   unsigned *out;
   CHECK(hipMalloc(&out, (size_t)cus * wps * 256 * 4));
   for (auto &p : probes()) {
+    const std::string name(p.first), id = "," + name.substr(0, name.find(':')) + ",";
+    if (argc > 2 && !strstr(("," + std::string(argv[2]) + ",").c_str(), id.c_str())) continue;  // ids: a,b,c
     hipLaunchKernelGGL(p.second, dim3(cus * wps), dim3(256), 0, 0, out);
     CHECK(hipDeviceSynchronize());
     printf("%s\n", p.first);

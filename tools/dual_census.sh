@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 hipcc --offload-arch=gfx950 -O3 tools/dual_census.hip -o /tmp/dual_census 2>/dev/null
 for w in ${WAVES:-1 4}; do
   timeout -s KILL 100 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU2 GRBM_GUI_ACTIVE -d "$OUT/w$w" -o pmc \
-    --output-format csv -- /tmp/dual_census $w > "$OUT/w$w.names" 2>&1
+    --output-format csv -- /tmp/dual_census $w ${FORMS:-} > "$OUT/w$w.names" 2>&1  # FORMS=id,id,...: those forms only
 done
 WS="${WAVES:-1 4}" python3 - "$OUT" <<'PY'
 import csv, glob, os, sys, collections

@@ -22,7 +22,8 @@
 //               two modes of a pair ride in the two 16-bit halves of each VGPR (packed
 //               v_pk_* int16 ops; all intermediates provably fit 16 bits).
 //   per pair  phase A: the reduced predictions of all CUs of the task for the pair, as
-//               16x16x16 f16 MFMAs (exact: integer inputs < 2^11, sums < 2^24), into a
+//               16x16x16 f16 MFMAs (exact: inputs of 11 bits, sums of under 24), converted
+//               and clipped two at a time (convert_pair) into a
 //               wave-private LDS scratch; phase B: every lane upsamples its strip window by
 //               window and computes SAD + SATD 4x4 block by 4x4 block; strips and row parts
 //               of a CU are combined with xor shuffles, one lane stores the two costs.
@@ -267,8 +268,9 @@ __device__ __forceinline__ CuPos cu_pos(const Job &j, int fx0, int fy0, const RT
 }
 
 // Reduced boundaries (intra.cl:71-73, 127-141, 202-204, 259-279: box downsampling; a
-// factor of 1 is a copy) -> the CU's MFMA input entry: f16 values 1024 + b for the
-// boundary vector b = (redT, redL) (f16 bit pattern 0x6400 | b, exact for b < 1024).  The
+// factor of 1 is a copy) -> the CU's MFMA input entry: f16 values 1 + b / 1024 for the
+// boundary vector b = (redT, redL) (f16 bit pattern 0x3C00 | b, exact for b < 1024: the tables'
+// input 1024 + b scaled by kPredScale, see phase_a).  The
 // transposed orientation (redL, redT) (intra.cl:417-418) is the same entry read with its
 // two 8-byte halves swapped; sizeId 0 stores (T0 T1 L0 L1 | L0 L1 T0 T1) for that.
 // The coefficient tables (mip_kernels.h) absorb p = b - b0, p_0 and the bias.
@@ -301,7 +303,7 @@ __device__ __forceinline__ void write_inputs(const CuPos &c, const RT &rt, uint8
     });
     redL[i] = c.left ? (l + rndL) >> l2L : c.padL;
   });
-  constexpr uint32_t kBias = 0x64006400u;  // f16 1024.0 in both halves
+  constexpr uint32_t kBias = 0x3C003C00u;  // f16 1.0 in both halves
   uint4 e;
   if constexpr (G::RBS == 4) {
     e = make_uint4(redT[0] | redT[1] << 16, redT[2] | redT[3] << 16, redL[0] | redL[1] << 16, redL[2] | redL[3] << 16);
@@ -593,19 +595,16 @@ struct Red {
   static constexpr int OFF = RP > R ? 1 : 0;  // padded rows: the left sample at kx = -1
   const uint32_t *p;
   int k0;
-  // phase A stores floor(D) saturated at 0 only; the clip to 1023 is applied here, to
-  // both modes of a pair at once
-  static __device__ __forceinline__ s2 clip(uint32_t v) {
-    return __builtin_bit_cast(s2, __builtin_elementwise_min(__builtin_bit_cast(u2, v), (u2){1023, 1023}));
-  }
-  __device__ __forceinline__ s2 operator()(int k, int kx) const { return clip(p[(k + k0) * RP + kx + OFF]); }
+  // phase A stores the samples clipped to [0, 1023] (convert_pair); the padded rows' left
+  // samples (write_left) are boundary samples
+  __device__ __forceinline__ s2 operator()(int k, int kx) const { return as_s2(p[(k + k0) * RP + kx + OFF]); }
   __device__ __forceinline__ void row4(int k, int kx, s2 (&out)[4]) const {  // kx % 4 == 0
     static_assert(RP == R, "row4 reads unpadded rows");
     const uint4 v = *reinterpret_cast<const uint4 *>(p + (k + k0) * R + kx);
-    out[0] = clip(v.x);
-    out[1] = clip(v.y);
-    out[2] = clip(v.z);
-    out[3] = clip(v.w);
+    out[0] = as_s2(v.x);
+    out[1] = as_s2(v.y);
+    out[2] = as_s2(v.z);
+    out[3] = as_s2(v.w);
   }
 };
 
@@ -1042,17 +1041,36 @@ struct Ctx {
   int fx0, fy0;               // quadrant origin in the frame
 };
 
-// floor(f) for f >= 0, 0 for f < 0: v_cvt_u32_f32 saturates out-of-range inputs.
-__device__ __forceinline__ uint32_t floor_sat(float f) { return (uint32_t)f; }
+// Phase A's conversion clips.  The MFMA does not deliver the unclipped reduced sample D (a
+// multiple of 1/64, |D| <= 8 * 1023 * 127 / 64 + 1023 < 2^16) but x = (D + kPredBeta) * kPredScale:
+// its B operand is 1 + b / 1024 instead of the tables' 1024 + b (write_inputs), its C operand
+// (C' + kPredBeta) * kPredScale (scaled_c: the kernel prologue rewrites the tables' f32 rows in
+// LDS); powers of two, so every product and partial sum stays exact (below 2^23 in units of
+// 2^-17).  v_cvt_pknorm_u16_f32 converts two x to u16 x * 65535, saturating at 0 and 65535:
+// with m = 64 D, x * 65535 = (m + 0.5) (1 - 2^-16) lies strictly inside (m - 0.5, m + 0.5), at
+// least 128 f32 ulps from both ends, so the conversion returns m, and m >> 6 = floor(D); x <= 0
+// gives 0 and x >= 1 gives 65535 >> 6 = 1023.  Two instructions for two samples,
+// min(max(floor(D), 0), 1023) in both halves: no clip is left for the readers (Red).
+// tools/pknorm_probe.hip checks the conversion over all 2^23 values (D + beta) / 1024 of the
+// grid and the MFMA's exactness with these operands on the hardware (profiles/pknorm_probe.txt:
+// "convert beta=2^-7: 0 mismatches over the kernel's values", "beta=2^-6: 1024 mismatches" --
+// the conversion rounds to nearest -- and "0 of ... results differ" for every size id).
+constexpr float kPredBeta = 1.0f / 128.0f, kPredScale = 1.0f / 1024.0f;
+__device__ __forceinline__ uint32_t scaled_c(uint32_t c_bits) {
+  return __builtin_bit_cast(uint32_t, (__builtin_bit_cast(float, c_bits) + kPredBeta) * kPredScale);
+}
+__device__ __forceinline__ uint32_t convert_pair(float x0, float x1) {
+  return as_u32(__builtin_bit_cast(u2, __builtin_amdgcn_cvt_pknorm_u16(x0, x1)) >> (u2){6, 6});
+}
 
 // Phase A for mode pair q: reduced predictions of every CU of the task,
 //   D[j][n] = C[j] + sum_k A[j][k] B[k][n]     (16x16x16 f16 MFMA, f32 accumulate, exact)
 // rows j = MIP matrix outputs, columns n = (CU 8*cs + n/2, mode 2q + n%2), K = the 8 inputs
 // of mode 2q (k < 8) and of mode 2q+1 (k >= 8), block-diagonal.  floor(D) clipped to
 // [0, 1023] equals the reference's clamp(((offset + sum p*w) >> 6) + b0) (intra.cl:449-482;
-// coefficient restatement in mip_kernels.h); phase A stores floor(D) saturated at 0 (D is
-// the unclipped sample, |D| <= 8 * 1023 * 127 / 64 + 1023 < 2^16) and Red applies the upper
-// clip to packed pairs on read.  Results go to scratch[pos][slot] (16-bit
+// coefficient restatement in mip_kernels.h); the conversion stores exactly that
+// (convert_pair: a lane's outputs i, i + 1 are converted together and stored as the two
+// halves of the result).  Results go to scratch[pos][slot] (16-bit
 // halves = modes), pos = stored position (transposed modes store output j at (j%R, j/R),
 // intra.cl:402-406, 485).  CHUNKED classes produce reduced rows [4*chunk, 4*chunk + 4).
 template <int W, int H, int V, bool TR>
@@ -1130,12 +1148,15 @@ __device__ __forceinline__ void phase_a(const Ctx &x, int lane, int ncu, int q, 
       // the class has fewer than 8 slots
       if ((G::SLOTS % 8 == 0 || 8 * cs + (r >> 1) < ncu) && (!HALF || TR || (h >> 1) == chunk)) {
         uint8_t *dst = lane_dst + (pofs + 8 * cs * G::PITCH) * 4;
-        static_for<4>([&](auto i_c) {
-          constexpr int i = decltype(i_c)::value;
-          constexpr int off = TR2 ? (i & 1) * G::R + (i >> 1) : i * PSTEP;
-          if (!(HALF && TR) || (i >> 1) == chunk) {
-            const uint32_t v = floor_sat(d[i]);  // < 2^16; the upper clip is applied by Red
-            *reinterpret_cast<uint16_t *>(dst + off * 4) = (uint16_t)v;
+        static_for<2>([&](auto ip_c) {  // outputs 2 ip, 2 ip + 1: the halves of one conversion
+          constexpr int ip = decltype(ip_c)::value;
+          if (!(HALF && TR) || ip == chunk) {
+            const uint32_t v = convert_pair(d[2 * ip], d[2 * ip + 1]);
+            static_for<2>([&](auto il_c) {  // (ds_write_b16 and ds_write_b16_d16_hi)
+              constexpr int i = 2 * ip + decltype(il_c)::value;
+              constexpr int off = TR2 ? (i & 1) * G::R + (i >> 1) : i * PSTEP;
+              *reinterpret_cast<uint16_t *>(dst + off * 4) = (uint16_t)(i & 1 ? v >> 16 : v);
+            });
           }
         });
       }
@@ -1150,10 +1171,11 @@ __device__ __forceinline__ void phase_a(const Ctx &x, int lane, int ncu, int q, 
 // phase_a would compute all 16 outputs of 8 CUs per MFMA and keep half).  K: the 8 inputs in
 // the first half, zeros in the second.
 // Row r = (mode r & 1, chunk position p = ((r >> 1) >> 1) + 4 ((r >> 1) & 1)), so a lane's
-// four results are both modes of positions h and h + 4 (h = lane >> 4) of CU lane & 15: the
-// 16-bit stores of one instruction hit 64 distinct words of a 12-word pitch (the first
-// version, rows = (mode, position), put two lanes on each word: 54 % LDS bank conflicts in the
-// 4x4 class).  Chunk position p is row p >> 2 (2c + (p >> 2) of the prediction), column p & 3;
+// four results are both modes of positions h and h + 4 (h = lane >> 4) of CU lane & 15: each
+// converted pair is one scratch word, and the 32-bit stores of one instruction hit 64 distinct
+// words of a 12-word pitch (the first version, rows = (mode, position), put two lanes on each
+// word: 54 % LDS bank conflicts in the 4x4 class).
+// Chunk position p is row p >> 2 (2c + (p >> 2) of the prediction), column p & 3;
 // untransposed it is output j = 8c + p, transposed (stored at (j % 4, j / 4)) output
 // j = 4 (p & 3) + 2c + (p >> 2).
 template <int W, int H, int V, bool TR>
@@ -1169,7 +1191,7 @@ __device__ __forceinline__ void phase_a_half(const Ctx &x, int lane, int q, int 
                               : x.zero;
   const h4 av = *reinterpret_cast<const h4 *>(aptr);
   // (lanes h >= 2 read the same entries' other half: finite f16 values -- an entry holds
-  // 1024 + b for every input -- times the zero A operand, so those K rows add exactly 0 to
+  // 1 + b / 1024 for every input -- times the zero A operand, so those K rows add exactly 0 to
   // the written CUs' columns; columns of slots >= ncu land in unused scratch rows)
   const uint8_t *bbase = x.wave + r * kEntryBytes + 8 * ((h & 1) ^ (TR ? 1 : 0));
   // C: rows 4h + i = (mode i & 1, position h + 4 (i >> 1))
@@ -1187,12 +1209,10 @@ __device__ __forceinline__ void phase_a_half(const Ctx &x, int lane, int q, int 
   for (int cs = 0; cs < 4; cs++) {
     const f4 d = __builtin_amdgcn_mfma_f32_16x16x16f16(av, bvs[cs], cin, 0, 0, 0);
     uint8_t *dst = lane_dst + 16 * cs * G::PITCH * 4;  // slots >= ncu: unused scratch rows
-    static_for<4>([&](auto i_c) {
-      constexpr int i = decltype(i_c)::value;
-      // (volatile LDS store: two 16-bit stores, not a v_perm-packed 32-bit one -- VALU is the bound)
-      typedef __attribute__((address_space(3))) volatile uint16_t lds_u16;
-      *(lds_u16 *)(dst + 16 * (i >> 1) + 2 * (i & 1)) = (uint16_t)floor_sat(d[i]);
-    });
+    // (d0, d1) and (d2, d3) are both modes of one position: a conversion's result is the
+    // scratch word
+    *reinterpret_cast<uint32_t *>(dst) = convert_pair(d[0], d[1]);
+    *reinterpret_cast<uint32_t *>(dst + 16) = convert_pair(d[2], d[3]);
   }
 }
 
@@ -1894,8 +1914,13 @@ __global__ __launch_bounds__(64 * NW, NW == kWideWaves ? 4 : kWavesPerSimd) void
   uint8_t *tab = smem + L.tables, *zero = smem + L.zero, *waves = smem + L.waves;
   uint32_t *counters = reinterpret_cast<uint32_t *>(smem + L.counters);
 
-  for (int i = threadIdx.x; i < kTableBytes / 16; i += blockDim.x)
-    reinterpret_cast<uint4 *>(tab)[i] = a.tables[i];
+  // the MIP tables; their f32 accumulator rows (from byte kWeightRows * 16) go into LDS as
+  // (C' + kPredBeta) * kPredScale (scaled_c)
+  for (int i = threadIdx.x; i < kTableBytes / 16; i += blockDim.x) {
+    uint4 v = a.tables[i];
+    if (i >= kWeightRows) v = make_uint4(scaled_c(v.x), scaled_c(v.y), scaled_c(v.z), scaled_c(v.w));
+    reinterpret_cast<uint4 *>(tab)[i] = v;
+  }
   for (int i = threadIdx.x; i < kZeroBytes / 16; i += blockDim.x)
     reinterpret_cast<uint4 *>(zero)[i] = make_uint4(0, 0, 0, 0);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
