@@ -348,6 +348,80 @@ int mip_partition_frames(mip_engine *e, const uint16_t *frames, const uint16_t *
                          const int32_t *penalty, uint8_t *best_mode_out, int32_t *best_cost_out,
                          uint8_t *leaf_out, int32_t *ctu_cost_out, int32_t *ctu_leaves_out);
 
+/* Planar / DC baseline costs and the MIP-vs-regular decision merge (additive to ABI 7; no
+ * reference counterpart -- the reference ranks MIP modes only).  VTM keeps MIP modes in one
+ * candidate list with the regular intra modes and ranks them by the same min(2*SAD, SATD);
+ * Planar and DC are the regular modes it always tries.  mip_intra_device gives every CU those
+ * two costs with the engine's own measure, so that "where does MIP win" and a partition that is
+ * not MIP-only need no host round trip.
+ *
+ * Definition, for the CU at frame position (x, y) of size w x h (lw = log2 w, lh = log2 h).  R
+ * is the reference frame with the source rule of mip_predict_device (d_refs NULL: the originals,
+ * or the engine's filter applied into engine scratch, nframes <= max_batch then; otherwise the
+ * caller's frames), F the original frame; both are read by linear index.
+ *
+ * Reference samples.  top[0..w) and left[0..h) are exactly the complete boundaries of the MIP
+ * path: top[i] = R[(y-1)*W + x+i], or on the first frame row R[x-1] (512 at x = 0); left[j] =
+ * R[(y+j)*W + x-1], or in the first frame column R[(y-1)*W] (512 at y = 0).  Above-right and
+ * below-left samples are treated as unavailable (their causal availability depends on the
+ * partition, which is not known here) and take VVC's substitution: topRight = top[w-1],
+ * bottomLeft = left[h-1].  The corner sample is never read.  So a CU reads no sample that its
+ * MIP search does not read, and the availability set is the search's: mip_unavailable_cus(width,
+ * height, filter), or the MIP_FILTER_NONE set with caller references.
+ *
+ * Planar (mode slot 0), sample (i, j):
+ *     predV = ((h-1-j)*top[i] + (j+1)*bottomLeft) << lw
+ *     predH = ((w-1-i)*left[j] + (i+1)*topRight) << lh
+ *     P     = (predV + predH + w*h) >> (lw + lh + 1)
+ * DC (mode slot 1), every sample:
+ *     w == h: P = (sum top + sum left + w) >> (lw+1)
+ *     w >  h: P = (sum top + (w>>1)) >> lw          h > w: P = (sum left + (h>>1)) >> lh
+ * PDPC, both modes:
+ *     scale = (lw + lh - 2) >> 2
+ *     sT = (2*j) >> scale, wT = sT <= 5 ? 32 >> sT : 0;  sL = (2*i) >> scale, wL likewise
+ *     out = clip(0, 1023, (left[j]*wL + top[i]*wT + (64 - wL - wT)*P + 32) >> 6)
+ * in 32-bit arithmetic throughout (engine-filtered references exceed 10 bits in the last columns
+ * at widths that are not multiples of 128; that is the only way the clip can fire).
+ *
+ * NOT modelled: VVC's [1 2 1] smoothing of Planar's reference samples for blocks of more than 32
+ * samples (it needs the corner and samples beyond w and h), the angular modes, multi-reference
+ * lines and ISP.
+ *
+ * Cost.  SAD and SATD of `out` against the CU's originals F[(y+j)*W + x+i] (CUs right of the
+ * frame wrap as in the cost tables), SATD the engine's: the 4x4 Hadamard per 4x4 block with the
+ * DC term >> 2 and (s + 1) >> 1 per block.  cost = min(2*SAD, SATD).
+ *
+ * Tables (device pointers, 8-byte aligned, each optional): d_cost, d_sad, d_satd are int32
+ * [nframes][nCTUs*5380][2] in the CU order of best_mode_out (ctu*5380 + shape CU prefix + cu),
+ * slot 0 Planar, slot 1 DC.  Every entry of a given table is written; unavailable CUs get
+ * MIP_COST_UNAVAILABLE in all three.
+ *
+ * Merge (optional; d_best_mode and d_best_cost are given together).  On entry d_best_mode /
+ * d_best_cost [nframes][nCTUs*5380] hold the K = 1 MIP decisions of mip_search_device or
+ * mip_topk_device.  bias is a HOST array of two int32 in 0 .. 1<<20 (NULL = zeros; anything else
+ * is an error before any launch): the caller's rate difference for signalling Planar / DC instead
+ * of a MIP mode.  Candidates are taken in the order MIP, Planar, DC; a later one replaces the
+ * current one only if cost + bias is strictly lower, and then writes mode MIP_MODE_PLANAR or
+ * MIP_MODE_DC and the biased cost.  Unavailable CUs (MIP_COST_UNAVAILABLE, mode 0xff) stay as
+ * they are.  Both mode constants are >= 2*modes of every shape, so mip_predict_device skips and
+ * counts such items under its existing write rule (emitting the Planar / DC blocks is a
+ * follow-up); the merged arrays feed mip_partition_device unchanged.
+ *
+ * At least one table or the merge pair must be given.  Asynchronous on `stream`; argument errors
+ * are reported before any launch. */
+#define MIP_MODE_PLANAR 0xf0
+#define MIP_MODE_DC 0xf1
+int mip_intra_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes,
+                     int32_t *d_cost, int32_t *d_sad, int32_t *d_satd, const int32_t *bias,
+                     uint8_t *d_best_mode, int32_t *d_best_cost, void *stream);
+
+/* The tables of host frames, synchronous like mip_predict_frames (it first waits for every call
+ * in flight; an open merged chunk is launched): in chunks of at most max_batch frames -- upload,
+ * filter if the engine has one and no references are given, kernel, download (no pipelining).
+ * cost_out / sad_out / satd_out: int32 [nframes][nCTUs*5380][2], each optional, at least one. */
+int mip_intra_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
+                     int32_t *cost_out, int32_t *sad_out, int32_t *satd_out);
+
 /* Streaming device-to-device copy of `bytes` (a multiple of 16, 16-byte aligned pointers),
  * asynchronous on `stream`: 16 bytes per lane, four loads in flight per lane -- the HBM copy
  * rate bench.py prices the filter kernel against (no reference counterpart). */

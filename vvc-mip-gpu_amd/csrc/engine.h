@@ -1,5 +1,5 @@
 // engine.h -- private to the library: the engine's state and what its two translation units
-// share (mipgpu.cpp: create / destroy, block cache, device API, prediction, partition;
+// share (mipgpu.cpp: create / destroy, block cache, device API, prediction, partition, intra;
 // host_pipeline.cpp: the host API's pipeline).
 #pragma once
 #include "mipgpu.h"
@@ -135,6 +135,10 @@ struct mip_engine {
   // max_batch frames: the leaf flags, and the CTU costs followed by the CTU leaf counts.
   uint8_t *d_part_leaf = nullptr;
   int32_t *d_part_ctu = nullptr;
+  // Planar / DC baseline costs (mip_intra_device), uploaded at its first use: the lane slots of
+  // the 16 32x32 blocks of a CTU (intra_plan.h intra_build_slots).
+  uint32_t *d_intra_slots = nullptr;
+  int intra_slots_per_block = 0;
   int resident[2] = {0, 0};  // persistent search grid (workgroups resident on this device), [alt]
   int resident_wide[2] = {0, 0};  // the same for 16-wave workgroups
   int resident_four[2] = {0, 0};  // the four-wave twin's (8-wave workgroups; 0: not available)

@@ -1,6 +1,6 @@
 // mip_kernels.h -- launch interface between the C-ABI host code (mipgpu.cpp, host_pipeline.cpp)
 // and the gfx950 kernels (mip_search.hip, mip_decide.hip, mip_filter.hip, mip_fixup.hip,
-// mip_predict.hip, mip_partition.hip).  Not part of the public ABI.
+// mip_predict.hip, mip_partition.hip, mip_intra.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -194,5 +194,21 @@ struct PartitionArgs {
   PartitionPenalty penalty;
 };
 hipError_t launch_partition(const PartitionArgs &a, hipStream_t s);
+
+// Planar / DC baseline costs and the decision merge (intra_kernel, mip_intra.hip): workgroups
+// stride over the (frame, CTU, 64x64 CU or 32x32 block) items.
+struct IntraArgs {
+  const uint16_t *orig;       // [nframes][height][width] original samples (distortion)
+  const uint16_t *refs;       // reference-sample source: == orig, the filtered or the caller's frames
+  const uint8_t *unavail;     // [nctus * 5380] 1 = the CU's entries are MIP_COST_UNAVAILABLE
+  const uint32_t *slots;      // [16][slots_per_block] lane slots (intra_plan.h intra_build_slots)
+  int slots_per_block;        // a multiple of 64
+  int32_t *cost, *sad, *satd; // optional tables [nframes][nctus * 5380][2], 8-byte aligned
+  uint8_t *best_mode;         // optional merge, both or neither: [nframes][nctus * 5380]
+  int32_t *best_cost;
+  int32_t bias[2];            // Planar, DC: 0 .. 1 << 20 (checked by the caller)
+  int width, height, ctu_cols, nctus, nframes;
+};
+hipError_t launch_intra(const IntraArgs &a, hipStream_t s);
 
 }  // namespace mipgpu

@@ -1,5 +1,6 @@
 // mipgpu.cpp -- C-ABI engine (include/mipgpu.h): device set-up, buffers, the upload of the
-// planned work lists (work_plan.h), the device API's launch sequence, prediction and partition.
+// planned work lists (work_plan.h), the device API's launch sequence, prediction, partition and
+// the Planar / DC baseline costs.
 // The host API's pipeline, which replaces main.cpp's OpenCL host loop: host_pipeline.cpp.
 #include "engine.h"
 
@@ -10,6 +11,7 @@
 #include <cstring>
 
 #include "mip_tables.h"
+#include "intra_plan.h"
 #include "partition_plan.h"
 
 thread_local std::string g_err;
@@ -358,6 +360,7 @@ int mip_engine_destroy(mip_engine *e) {
   dev_free(e->d_pred_geo);
   dev_free(e->d_part_leaf);
   dev_free(e->d_part_ctu);
+  dev_free(e->d_intra_slots);
   dev_free(e->d_queue);
   if (e->h_status) (void)hipHostFree(e->h_status);
   if (e->h_frame_status) (void)hipHostFree(e->h_frame_status);
@@ -1189,6 +1192,138 @@ int mip_partition_frames(mip_engine *e, const uint16_t *frames, const uint16_t *
 #undef PART_TRY
   e->refs_pending = false;
   if (const uint32_t f = take_status(e, mip_engine::kCallRing)) return done(contract_error(f, "mip_partition_frames"));
+  return done(0);
+}
+
+// ---------------------------------------------------------------- Planar / DC baseline costs
+// The engine's lane-slot table (mip_engine::d_intra_slots), uploaded once, and the prediction
+// tables' availability sets.
+static int ensure_intra_tables(mip_engine *e) {
+  if (ensure_pred_tables(e) != 0) return -1;
+  if (e->d_intra_slots) return 0;
+  int per_block = 0;
+  const std::vector<uint32_t> slots = mipgpu::intra_build_slots(&per_block);
+  if (slots.empty()) return fail("intra: the CU shapes do not fit the 32x32 blocks");
+  uint32_t *d = nullptr;
+  HIP_TRY(dev_malloc(e->device, (void **)&d, slots.size() * sizeof(uint32_t)));
+  if (hipMemcpy(d, slots.data(), slots.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+    dev_free(d);
+    return fail("uploading the intra lane slots failed");
+  }
+  e->intra_slots_per_block = per_block;
+  e->d_intra_slots = d;  // (set last: the table is complete)
+  return 0;
+}
+
+// The argument rules of both intra entry points (before any launch).
+static int intra_args_ok(const mip_engine *e, int nframes, bool any_output) {
+  if (nframes < 1) return fail("bad intra arguments");
+  if (!any_output) return fail("intra: no output given");
+  if ((long long)nframes * e->nctus * MIP_CUS_PER_CTU > kMaxCus) return fail("%d frames exceed %lld CUs per call", nframes, kMaxCus);
+  return 0;
+}
+
+int mip_intra_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes, int32_t *d_cost,
+                     int32_t *d_sad, int32_t *d_satd, const int32_t *bias, uint8_t *d_best_mode, int32_t *d_best_cost,
+                     void *stream) {
+  if (!e) return fail("engine is NULL");
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (!d_frames) return fail("bad intra arguments: no frames");
+  if (intra_args_ok(e, nframes, d_cost || d_sad || d_satd || d_best_mode || d_best_cost) != 0) return -1;
+  if (!d_best_mode != !d_best_cost) return fail("intra: d_best_mode and d_best_cost are given together");
+  if (!mipgpu::intra_bias_ok(bias)) return fail("intra: a bias is outside 0..%d", (int)mipgpu::kIntraMaxBias);
+  for (const void *p : {(const void *)d_cost, (const void *)d_sad, (const void *)d_satd})
+    if (reinterpret_cast<uintptr_t>(p) & 7) return fail("intra: the tables must be 8-byte aligned");
+  HIP_TRY(hipSetDevice(e->device));
+  if (flush_open(e) != 0) return -1;  // (device-API work orders itself after the host calls)
+  if (ensure_intra_tables(e) != 0) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  const uint16_t *refs = d_refs ? d_refs : d_frames;
+  const bool engine_refs = !d_refs && e->opts.filter != MIP_FILTER_NONE;
+  if (engine_refs) {  // as mip_predict_device: filter into the engine's reference scratch
+    if (nframes > e->opts.max_batch) return fail("nframes %d > max_batch %d", nframes, e->opts.max_batch);
+    if (e->refs_pending) HIP_TRY(hipStreamWaitEvent(s, e->refs_done, 0));
+    if (e->host_pending)
+      HIP_TRY(hipStreamWaitEvent(s, e->call_done[(e->host_calls - 1) % mip_engine::kCallRing], 0));
+    if (mip_filter_device(d_frames, e->d_refs, e->width, e->height, nframes, e->opts.filter, e->opts.kernel_idx, s) != 0)
+      return -1;
+    refs = e->d_refs;
+  }
+  mipgpu::IntraArgs a{};
+  a.orig = d_frames;
+  a.refs = refs;
+  a.unavail = e->d_pred_unavail[engine_refs ? 1 : 0];
+  a.slots = e->d_intra_slots;
+  a.slots_per_block = e->intra_slots_per_block;
+  a.cost = d_cost;
+  a.sad = d_sad;
+  a.satd = d_satd;
+  a.best_mode = d_best_mode;
+  a.best_cost = d_best_cost;
+  for (int k = 0; k < mipgpu::kIntraModes; k++) a.bias[k] = bias ? bias[k] : 0;
+  a.width = e->width;
+  a.height = e->height;
+  a.ctu_cols = e->ctu_cols;
+  a.nctus = e->nctus;
+  a.nframes = nframes;
+  HIP_TRY(mipgpu::launch_intra(a, s));
+  if (engine_refs) {
+    HIP_TRY(hipEventRecord(e->refs_done, s));
+    e->refs_pending = true;
+  }
+  return 0;
+}
+
+int mip_intra_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes, int32_t *cost_out,
+                     int32_t *sad_out, int32_t *satd_out) {
+  if (!e) return fail("engine is NULL");
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (!frames) return fail("bad intra arguments: no frames");
+  if (intra_args_ok(e, nframes, cost_out || sad_out || satd_out) != 0) return -1;
+  HIP_TRY(hipSetDevice(e->device));
+  if (quiesce(e) != 0) return -1;  // (host searches in flight use the engine buffers)
+  const size_t fs = (size_t)e->width * e->height, mb = (size_t)e->opts.max_batch;
+  const size_t entries = (size_t)e->nctus * MIP_CUS_PER_CTU * mipgpu::kIntraModes;  // per frame and table
+  // the call's own device buffers (through the device block cache): caller references on an
+  // engine without a reference buffer, and one table of max_batch frames per output asked for
+  int32_t *const host_out[3] = {cost_out, sad_out, satd_out};
+  uint16_t *t_refs = nullptr;
+  int32_t *d_out[3] = {nullptr, nullptr, nullptr};
+  auto done = [&](int rc) {
+    for (void *p : {(void *)t_refs, (void *)d_out[0], (void *)d_out[1], (void *)d_out[2]}) dev_free(p);
+    return rc;
+  };
+#define INTRA_TRY(expr)                                                                    \
+  do {                                                                                     \
+    hipError_t _e = (expr);                                                                \
+    if (_e != hipSuccess) return done(fail("%s: %s", #expr, hipGetErrorString(_e)));       \
+  } while (0)
+  uint16_t *d_refs = nullptr;
+  if (refs_or_null) {
+    d_refs = e->d_refs;
+    if (!d_refs) {
+      INTRA_TRY(dev_malloc(e->device, (void **)&t_refs, mb * fs * 2));
+      d_refs = t_refs;
+    }
+  }
+  const size_t chunk = std::min(mb, (size_t)nframes);
+  for (int t = 0; t < 3; t++)
+    if (host_out[t]) INTRA_TRY(dev_malloc(e->device, (void **)&d_out[t], chunk * entries * sizeof(int32_t)));
+  hipStream_t s = e->stream;
+  for (int f0 = 0; f0 < nframes; f0 += e->opts.max_batch) {
+    const size_t nb = (size_t)std::min(e->opts.max_batch, nframes - f0);
+    INTRA_TRY(hipMemcpyAsync(e->d_frames, frames + f0 * fs, nb * fs * 2, hipMemcpyHostToDevice, s));
+    if (d_refs) INTRA_TRY(hipMemcpyAsync(d_refs, refs_or_null + f0 * fs, nb * fs * 2, hipMemcpyHostToDevice, s));
+    // (without references the device entry point filters the frames itself when the engine has a filter)
+    if (mip_intra_device(e, e->d_frames, d_refs, (int)nb, d_out[0], d_out[1], d_out[2], nullptr, nullptr, nullptr, s) != 0)
+      return done(-1);
+    for (int t = 0; t < 3; t++)
+      if (host_out[t])
+        INTRA_TRY(hipMemcpyAsync(host_out[t] + f0 * entries, d_out[t], nb * entries * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    INTRA_TRY(hipStreamSynchronize(s));
+  }
+#undef INTRA_TRY
+  e->refs_pending = false;
   return done(0);
 }
 

@@ -61,6 +61,9 @@ PRED_LAYOUTS = {"packed": 0, "frame": 1}   # MIP_PRED_PACKED / MIP_PRED_FRAME
 PRED_NONE = 0xFFFF                         # MIP_PRED_NONE: host output samples no item wrote
 PART_MAX_LEAVES = 1024                     # MIP_PART_MAX_LEAVES: list entries per CTU of partition_device
 PART_MAX_PENALTY = 1 << 20                 # per-shape penalties of the partition decision: 0 .. 1<<20
+MODE_PLANAR = 0xF0                         # MIP_MODE_PLANAR / MIP_MODE_DC: best_mode values written by the
+MODE_DC = 0xF1                             # merge of intra_device (regular intra modes, not MIP modes)
+INTRA_MAX_BIAS = 1 << 20                   # biases of that merge: 0 .. 1<<20
 
 
 class _Opts(ctypes.Structure):
@@ -144,6 +147,8 @@ def library():
         "mip_predict_frames": (ip, [vp, vp, vp, ip, vp, i64, vp, i64, ctypes.POINTER(i64)]),
         "mip_partition_device": (ip, [vp, vp, ip, ip, ip, vp, vp, vp, vp, vp, vp]),
         "mip_partition_frames": (ip, [vp, vp, vp, ip, vp, vp, vp, vp, vp, vp]),
+        "mip_intra_device": (ip, [vp, vp, vp, ip, vp, vp, vp, vp, vp, vp, vp]),
+        "mip_intra_frames": (ip, [vp, vp, vp, ip, vp, vp, vp]),
         "mip_time_search_device": (ctypes.c_double, [vp, vp, vp, ip, vp, ip]),
         "mip_host_stats": (ip, [vp, ctypes.POINTER(ctypes.c_uint64), ip]),
         "mip_search_census": (ip, [vp, ctypes.POINTER(ctypes.c_uint64), ip]),
@@ -481,6 +486,43 @@ class MipEngine:
                                                   _ptr(res["ctu_leaves"])))
         return res
 
+    # ------------------------------------------- Planar / DC baseline costs
+    def intra(self, frames, refs=None, sad_satd=False) -> dict:
+        """Planar / DC baseline costs of host frames (mip_intra_frames, contract in
+        include/mipgpu.h): dict of numpy int32 arrays [F, nCTUs*5380, 2] -- 'cost' (slot 0 Planar,
+        slot 1 DC; UNAVAILABLE for unavailable CUs) and, with sad_satd, 'sad' / 'satd'."""
+        f = self._frames(frames)
+        r = None if refs is None else self._frames(refs)
+        n = f.shape[0]
+        res = {k: np.empty((n, self.cus_per_frame, 2), np.int32) for k in (("cost", "sad", "satd") if sad_satd else ("cost",))}
+        with self._lock:
+            _check(library().mip_intra_frames(self._h, _ptr(f), _ptr(r), n, _ptr(res["cost"]), _ptr(res.get("sad")),
+                                              _ptr(res.get("satd"))))
+        return res
+
+    def intra_device(self, frames, cost=None, sad=None, satd=None, refs=None, bias=None, best_mode=None, best_cost=None,
+                     stream=None):
+        """Asynchronous Planar / DC baseline costs and decision merge on device tensors
+        (mip_intra_device): `cost` / `sad` / `satd` int32 [F, nCTUs*5380, 2], each optional;
+        `best_mode` uint8 / `best_cost` int32 [F, nCTUs*5380] (given together) hold the K = 1 MIP
+        decisions of search_device and are merged in place -- a CU whose Planar (DC) cost plus
+        bias[0] (bias[1]), 0 .. 1<<20, is strictly lower gets MODE_PLANAR (MODE_DC) and that cost.
+        When nothing is asked for, `cost` is allocated.  Returns `cost`."""
+        import torch
+        n = frames.shape[0]
+        if cost is None and sad is None and satd is None and best_mode is None and best_cost is None:
+            cost = torch.empty((n, self.cus_per_frame, 2), dtype=torch.int32, device=frames.device)
+        want = {"cost": (cost, 8), "sad": (sad, 8), "satd": (satd, 8), "best_mode": (best_mode, 1), "best_cost": (best_cost, 4)}
+        for name, (t, size) in want.items():
+            if t is not None and (t.numel() * t.element_size() != n * self.cus_per_frame * size or not t.is_contiguous()):
+                raise MipError(f"intra_device: {name} must be a contiguous tensor of {n * self.cus_per_frame * size} bytes")
+        s = stream if stream is not None else torch.cuda.current_stream(frames.device)
+        with self._lock:
+            _check(library().mip_intra_device(self._h, _ptr(frames), _ptr(refs), n, _ptr(cost), _ptr(sad), _ptr(satd),
+                                              _ptr(_bias(bias)), _ptr(best_mode), _ptr(best_cost),
+                                              ctypes.c_void_p(s.cuda_stream)))
+        return cost
+
     def time_search_device(self, frames, costs, refs=None, reps=10) -> float:
         with self._lock:
             ms = library().mip_time_search_device(self._h, _ptr(frames), _ptr(refs), frames.shape[0], _ptr(costs),
@@ -567,6 +609,19 @@ def _penalty(penalty):
     return np.ascontiguousarray(p, dtype=np.int32)
 
 
+def _bias(bias):
+    """The merge biases of intra_device as the int32 [2] host array of the C ABI (None: zeros):
+    (Planar, DC).  The range is checked by the library."""
+    if bias is None:
+        return None
+    b = np.asarray(bias)
+    if b.shape != (2,):
+        raise MipError("bias must be two values (Planar, DC)")
+    if np.any(b != np.clip(b, -(1 << 31), (1 << 31) - 1)):
+        raise MipError("bias does not fit int32")
+    return np.ascontiguousarray(b, dtype=np.int32)
+
+
 def partition_device(best_cost, width, height, penalty=None, best_mode=None, leaf=None, ctu_cost=None, ctu_leaves=None,
                      items=None, stream=None):
     """CTU partition decision on device tensors (mip_partition_device, contract in
@@ -611,6 +666,6 @@ def filter_device(frames_in, frames_out, filter, kernel_idx=0, stream=None):
     return frames_out
 
 
-__all__ = ["PRED_ITEM", "PRED_NONE", "pred_items", "PART_MAX_LEAVES", "PART_MAX_PENALTY", "partition_device", "MipEngine", "MipError", "build_id", "source_id", "FILTERS", "FILTER_NONE", "filter_index", "filter_device", "topk_device", "library",
+__all__ = ["MODE_PLANAR", "MODE_DC", "INTRA_MAX_BIAS", "PRED_ITEM", "PRED_NONE", "pred_items", "PART_MAX_LEAVES", "PART_MAX_PENALTY", "partition_device", "MipEngine", "MipError", "build_id", "source_id", "FILTERS", "FILTER_NONE", "filter_index", "filter_device", "topk_device", "library",
            "pinned_empty", "unavailable_cus", "numa_node", "bind_thread", "device_cache", "copy_device",
            "layout", "SHAPES", "COSTS_PER_CTU", "CUS_PER_CTU", "UNAVAILABLE", "num_ctus"]
