@@ -267,3 +267,105 @@ def test_second_geometry_two_frames(gpu_available):
     for key in C.TABLES:
         assert np.array_equal(got[key], ref[key]), key
     assert not np.array_equal(got["cost"][0], got["cost"][1])
+
+
+def _odd_view(a):
+    """Device copy of `a` (uint16 frames) that starts at element 1 of a larger buffer: the device
+    pointer is 2-byte but not 4-byte aligned."""
+    import torch
+    src = _dev(a)
+    buf = torch.zeros(src.numel() + 8, dtype=src.dtype, device="cuda")
+    view = buf[1:1 + src.numel()].view(src.shape)
+    view.copy_(src)
+    assert view.data_ptr() % 4 == 2 and view.is_contiguous()
+    return view
+
+
+def test_unaligned_frames_and_references(gpu_available):
+    """The kernel stages frames and references with 2-byte loads, so it asks no alignment of
+    the caller's frames (mip_intra.hip header): frames, and frames plus caller references, at an
+    odd sample offset give the tables of the aligned call."""
+    w, h = 136, 72
+    frames, _, un, ref = C.case(w, h, None)
+    caller = frames[::-1]                                     # another frame's samples as references
+    want = [I.tables(f, r, un) for f, r in zip(frames[:2], caller[:2])]
+    with MipEngine(w, h, max_batch=3) as eng:
+        arena = Arena(3, eng.cus_per_frame)
+        eng.intra_device(_odd_view(frames), **{k: arena.tensor(k) for k in C.TABLES})
+        got, clean = arena.read(C.TABLES)
+        arena_r = Arena(2, eng.cus_per_frame)
+        eng.intra_device(_odd_view(frames[:2]), refs=_odd_view(caller[:2]), **{k: arena_r.tensor(k) for k in C.TABLES})
+        got_r, clean_r = arena_r.read(C.TABLES)
+    assert clean and clean_r
+    for key in C.TABLES:
+        assert np.array_equal(got[key], ref[key]), key
+        assert np.array_equal(got_r[key], np.stack([t[key] for t in want])), key
+    assert not np.array_equal(got_r["cost"], got["cost"][:2])
+
+
+def test_intra_and_search_share_the_filter_scratch_on_two_streams(gpu_available):
+    """intra_device on one stream and search_device on another, both filtering into the engine's
+    reference scratch (no caller references), different frames, alternating: each launch waits
+    for the previous reader of the scratch (refs_done), so each gives its own reference."""
+    import torch
+    import oracle_lib as O
+    from mipgpu.synth import synth_frames
+    w, h = 136, 72
+    frames, _, un, ref = C.case(w, h, FILTER)
+    other = synth_frames(w, h, 2, 0x2B7, 0)
+    want = np.stack([O.engine_search(f, FILTER, 0) for f in other])
+    assert not np.array_equal(other[0], frames[0])
+    rounds = 6
+    with MipEngine(w, h, filter=FILTER, max_batch=3) as eng:
+        d_intra = [_dev(np.roll(frames, -i, axis=0)) for i in range(3)]
+        d_search = [_dev(other[::s]) for s in (1, -1)]
+        arenas = [Arena(3, eng.cus_per_frame) for _ in range(rounds)]
+        costs = [torch.full((2, eng.costs_per_frame), -7, dtype=torch.int32, device="cuda") for _ in range(rounds)]
+        torch.cuda.synchronize()                              # inputs and prefills ran on the current stream
+        s_intra, s_search = torch.cuda.Stream(), torch.cuda.Stream()
+        for i in range(rounds):
+            eng.intra_device(d_intra[i % 3], stream=s_intra, **{k: arenas[i].tensor(k) for k in C.TABLES})
+            eng.search_device(d_search[i % 2], costs=costs[i], stream=s_search)
+        torch.cuda.synchronize()
+        eng.check_input(stream=s_search)
+        for i in range(rounds):
+            got, clean = arenas[i].read(C.TABLES)
+            assert clean, i
+            for key in C.TABLES:
+                assert np.array_equal(got[key], np.roll(ref[key], -(i % 3), axis=0)), (i, key)
+            assert np.array_equal(costs[i].cpu().numpy(), want[::1 if i % 2 == 0 else -1]), i
+
+
+def test_bad_arguments_fail_before_any_launch(gpu_available):
+    """More frames than max_batch on an engine that filters, a table pointer that is 4-byte but
+    not 8-byte aligned, and no output at all: an error each, nothing written."""
+    import ctypes
+    import torch
+    w, h = 136, 72
+    frames = C.frames(w, h)
+    with MipEngine(w, h, filter=FILTER, max_batch=2) as eng:
+        n = eng.cus_per_frame
+        d_frames = _dev(frames)
+        arena = Arena(3, n)
+        bm = torch.full((3, n), 0x5A, dtype=torch.uint8, device="cuda")
+        bc = torch.full((3, n), -3, dtype=torch.int32, device="cuda")
+        with pytest.raises(mipgpu.MipError, match="max_batch"):
+            eng.intra_device(d_frames, best_mode=bm, best_cost=bc, **{k: arena.tensor(k) for k in C.TABLES})
+        for key in C.TABLES:                                  # one table 4 bytes off, the others as they should be
+            outs = {k: arena.tensor(k)[:2 * n * 2] for k in C.TABLES}
+            outs[key] = arena.buf[arena.at[key] + 1:arena.at[key] + 1 + 2 * n * 2]
+            assert outs[key].data_ptr() % 8 == 4
+            with pytest.raises(mipgpu.MipError, match="8-byte aligned"):
+                eng.intra_device(d_frames[:2], best_mode=bm[:2], best_cost=bc[:2], **outs)
+        # no output: the Python call would allocate `cost`, so this one goes to the C entry point
+        s = torch.cuda.current_stream()
+        rc = mipgpu.library().mip_intra_device(eng._h, d_frames.data_ptr(), None, 2, None, None, None, None, None, None,
+                                               ctypes.c_void_p(s.cuda_stream))
+        assert rc != 0 and "no output" in mipgpu.library().mip_last_error().decode()
+        _, clean = arena.read(())
+        assert clean
+        assert torch.all(bm == 0x5A) and torch.all(bc == -3)
+        # the engine still works
+        got = eng.intra_device(d_frames[:2])
+        torch.cuda.synchronize()
+        assert np.array_equal(got.cpu().numpy(), C.case(w, h, FILTER)[3]["cost"][:2])

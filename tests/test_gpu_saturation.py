@@ -101,8 +101,8 @@ def _unclipped(refs):
 def test_restatement_is_the_oracle_reduced_prediction():
     """The restatement against oracle/mip_oracle.c's mipo_reduced_pred on random boundaries: equal
     after the clip (and as a multiset per mode: the oracle stores transposed modes transposed)."""
-    import ctypes
-    L = O.lib()
+    import predict_ref
+    L = predict_ref._lib()     # (the oracle with mipo_reduced_pred's argument types set: the same call whichever test ran first)
     rng = np.random.default_rng(11)
     for sid, (modes, r, rbs) in {0: (16, 4, 2), 1: (8, 4, 4), 2: (6, 8, 4)}.items():
         wm = _matrices()[sid]
@@ -115,8 +115,7 @@ def test_restatement_is_the_oracle_reduced_prediction():
                 mine = np.clip(((32 - 32 * p.sum() + wm @ p) >> 6) + b[0], 0, 1023)  # [modes, r * r]
                 for m in range(modes):
                     pred = np.zeros(r * r, np.int16)
-                    L.mipo_reduced_pred(sid, m, tr, rt.ctypes.data_as(ctypes.c_void_p), rl.ctypes.data_as(ctypes.c_void_p),
-                                        pred.ctypes.data_as(ctypes.c_void_p))
+                    L.mipo_reduced_pred(sid, m, tr, rt, rl, pred)
                     want = pred.reshape(r, r).T.reshape(-1) if tr else pred
                     assert np.array_equal(mine[m], want), (sid, m, tr)
 
