@@ -280,6 +280,28 @@ int mip_predict_frames(mip_engine *e, const uint16_t *frames, const uint16_t *re
                        const mip_pred_item *items, int64_t n, uint16_t *out, int64_t out_samples,
                        int64_t *skipped);
 
+/* Prediction with flags (additive to ABI 7).  flags == 0: exactly mip_predict_device /
+ * mip_predict_frames -- outputs, skipped count and errors (those entry points are flags == 0 calls
+ * of these).  Any bit other than MIP_PRED_REGULAR is an error before any launch.
+ *
+ * MIP_PRED_REGULAR: the mode condition of the write rule gains one alternative -- mode ==
+ * MIP_MODE_PLANAR or mode == MIP_MODE_DC (defined with mip_intra_device below) is valid for every
+ * shape, 64x64 included; every other condition is unchanged.  Such an item's samples are exactly
+ * the `out` of the Planar / DC / PDPC definition under mip_intra_device: top and left are the MIP
+ * path's complete boundaries, topRight = top[w-1], bottomLeft = left[h-1], 32-bit arithmetic,
+ * clipped to 0..1023, the reference frame read by linear index.  Reference source and availability
+ * set are those of mip_predict_device; the originals are not read (with d_refs / refs given the
+ * frames may be NULL).  So the SAD, SATD and min(2*SAD, SATD) of an emitted block against the
+ * original samples are the mip_intra_device table entries of that CU and slot (0 Planar, 1 DC),
+ * and the device list of mip_partition_device on merged decisions gives whole predicted frames. */
+#define MIP_PRED_REGULAR 1u   /* flags bit: items with mode MIP_MODE_PLANAR / MIP_MODE_DC are emitted */
+int mip_predict_device_ex(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes,
+                          const mip_pred_item *d_items, int64_t n, uint16_t *d_out, int64_t out_samples,
+                          uint32_t *d_skipped, unsigned flags, void *stream);
+int mip_predict_frames_ex(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
+                          const mip_pred_item *items, int64_t n, uint16_t *out, int64_t out_samples,
+                          unsigned flags, int64_t *skipped);
+
 /* CTU partition decision (additive to ABI 7; no reference counterpart -- the reference stops at
  * the cost table): which CUs to use.  The 47 CU shapes are closed under VTM's intra partition
  * defaults for a 128x128 CTU -- quad-tree splits down to 8x8, binary and ternary splits only
@@ -404,8 +426,8 @@ int mip_partition_frames(mip_engine *e, const uint16_t *frames, const uint16_t *
  * current one only if cost + bias is strictly lower, and then writes mode MIP_MODE_PLANAR or
  * MIP_MODE_DC and the biased cost.  Unavailable CUs (MIP_COST_UNAVAILABLE, mode 0xff) stay as
  * they are.  Both mode constants are >= 2*modes of every shape, so mip_predict_device skips and
- * counts such items under its existing write rule (emitting the Planar / DC blocks is a
- * follow-up); the merged arrays feed mip_partition_device unchanged.
+ * counts such items under its write rule; mip_predict_device_ex with MIP_PRED_REGULAR emits their
+ * Planar / DC blocks.  The merged arrays feed mip_partition_device unchanged.
  *
  * At least one table or the merge pair must be given.  Asynchronous on `stream`; argument errors
  * are reported before any launch. */
@@ -421,6 +443,21 @@ int mip_intra_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_
  * cost_out / sad_out / satd_out: int32 [nframes][nCTUs*5380][2], each optional, at least one. */
 int mip_intra_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
                      int32_t *cost_out, int32_t *sad_out, int32_t *satd_out);
+
+/* The whole chain on host frames, synchronous like mip_partition_frames (it first waits for every
+ * call in flight; an open merged chunk is launched): in chunks of at most max_batch frames --
+ * upload, filter if the engine has one and no references are given, decisions-only search, the
+ * merge of mip_intra_device with `bias` (NULL = zeros), mip_partition_device with `penalty`,
+ * MIP_PRED_REGULAR prediction of the partition's own device list into frame canvases preset to
+ * MIP_PRED_NONE, download.  Needs opts.best_k <= 1.  best_mode_out / best_cost_out (the merged
+ * decisions), leaf_out, ctu_cost_out, ctu_leaves_out as in mip_partition_frames; pred_out: uint16
+ * [nframes][H][W], the leaves' predicted samples at their place -- samples no leaf covers (CTUs
+ * without a partition) stay MIP_PRED_NONE.  Every output is optional, at least one must be given.
+ * A penalty or bias out of range is an error before any launch. */
+int mip_predicted_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
+                         const int32_t *penalty, const int32_t *bias,
+                         uint8_t *best_mode_out, int32_t *best_cost_out, uint8_t *leaf_out,
+                         int32_t *ctu_cost_out, int32_t *ctu_leaves_out, uint16_t *pred_out);
 
 /* Streaming device-to-device copy of `bytes` (a multiple of 16, 16-byte aligned pointers),
  * asynchronous on `stream`: 16 bytes per lane, four loads in flight per lane -- the HBM copy

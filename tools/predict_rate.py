@@ -4,7 +4,11 @@ frames, against two yardsticks measured in the same process: mip_copy_device of 
 of output bytes, and the search (mip_time_search_device) per frame at the same batch.
 
 Tilings, frame layout, best mode of every available CU of one shape: 64x64, 16x16, 4x4.  Packed:
-every mode of every 16x16 CU of one frame.  HIP events per launch, warm-up first, median of
+every mode of every 16x16 CU of one frame.  Those four go through mip_predict_device (the MIP-only
+kernel instance).  Two more go through mip_predict_device_ex with MIP_PRED_REGULAR: Planar for every
+available 16x16 CU, and the item list mip_partition_device writes for the 16 frames after the
+Planar / DC merge (bias CHAIN_BIAS, penalty CHAIN_PENALTY; padding entries included, as a caller
+that makes no host round trip passes it).  HIP events per launch, warm-up first, median of
 REPS launches.  Writes the record (with mip_build_id()) to --out, default
 profiles/predict_rate.txt."""
 import argparse
@@ -22,6 +26,7 @@ from mipgpu import MipEngine, copy_device, layout  # noqa: E402
 from mipgpu.synth import synth_frames_torch  # noqa: E402
 
 W, H, B, REPS, WARMUP = 1920, 1080, 16, 30, 5
+CHAIN_BIAS, CHAIN_PENALTY = (30, 30), 600
 
 
 def median_ms(fn, stream):
@@ -64,20 +69,25 @@ def main():
         canvas = torch.zeros(B * H * W, dtype=torch.int16, device=dev)
         scratch = torch.empty_like(canvas)
 
-        def run(name, items, out, nframes_of_case):
+        def run(name, items, out, nframes_of_case, regular=False):
+            # (regular=False passes no keyword: the four MIP cases run on older libraries too)
+            kw = {"regular": True} if regular else {}
             d_items = torch.from_numpy(items.view(np.uint8)).to(dev)
             sk = torch.zeros(1, dtype=torch.int32, device=dev)
-            eng.predict_device(frames, d_items, out, skipped=sk, stream=stream)
+            eng.predict_device(frames, d_items, out, skipped=sk, stream=stream, **kw)
             torch.cuda.synchronize()
-            assert int(sk.item()) == 0, (name, int(sk.item()))
-            ms = median_ms(lambda: eng.predict_device(frames, d_items, out, stream=stream), stream)
+            padding = items["frame"] < 0                      # (a partition list's unused entries)
+            assert int(sk.item()) == int(padding.sum()), (name, int(sk.item()))
+            ms = median_ms(lambda: eng.predict_device(frames, d_items, out, stream=stream, **kw), stream)
+            items = items[~padding]
             shape = layout.cu_geometry(W, H, items["cu"])
             nbytes = int((shape[3].astype(np.int64) * shape[4]).sum()) * 2
             nbytes16 = (nbytes + 15) // 16 * 16
             src, dst = canvas.view(torch.uint8)[:nbytes16], scratch.view(torch.uint8)[:nbytes16]
             copy_ms = median_ms(lambda: copy_device(src, dst, stream=stream), stream)
             lines.append("%-28s %9d %10.2f %9.4f %9.4f %10.2f %11.3f" % (
-                name, items.size, nbytes / 1e6, ms, copy_ms, ms / copy_ms, ms / nframes_of_case / search_ms))
+                name, d_items.numel() // mipgpu.PRED_ITEM.itemsize, nbytes / 1e6, ms, copy_ms, ms / copy_ms,
+                ms / nframes_of_case / search_ms))
 
         for sname in ("ALL_AL_64x64", "ALL_AL_16x16", "ALL_AL_4x4"):
             s = layout.SHAPE_BY_NAME[sname]
@@ -94,6 +104,22 @@ def main():
         mode = np.tile(np.arange(s.total_modes), ctu.size)
         items, total = mipgpu.pred_items(W, H, 0, cu, mode, nframes=B)
         run("packed, all modes, 16x16, 1 fr", items, canvas[:total], 1)
+        # regular items (MIP_PRED_REGULAR)
+        frame = np.repeat(np.arange(B), ctu.size)
+        cu_all = np.tile(ctu * layout.CUS_PER_CTU + prefix[s.index] + c, B)
+        items, total = mipgpu.pred_items(W, H, frame, cu_all, mipgpu.MODE_PLANAR, layout="frame", nframes=B)
+        run("frame, Planar, 16x16", items, canvas, B, regular=True)
+        d_best = torch.empty((B, eng.cus_per_frame), dtype=torch.uint8, device=dev)
+        eng.search_device(frames, costs=False, best_mode=d_best, best_cost=best_cost)
+        eng.intra_device(frames, bias=CHAIN_BIAS, best_mode=d_best, best_cost=best_cost)
+        d_list = torch.zeros((B, nct, mipgpu.PART_MAX_LEAVES * mipgpu.PRED_ITEM.itemsize), dtype=torch.uint8, device=dev)
+        mipgpu.partition_device(best_cost, W, H, penalty=CHAIN_PENALTY, best_mode=d_best, items=d_list)
+        torch.cuda.synchronize()
+        items = d_list.cpu().numpy().reshape(-1).view(mipgpu.PRED_ITEM)
+        leaves = items[items["frame"] >= 0]
+        n_regular = int(np.isin(leaves["mode"], (mipgpu.MODE_PLANAR, mipgpu.MODE_DC)).sum())
+        run("frame, merged partition list", items, canvas, B, regular=True)
+        lines.append("merged partition list: %d leaves (%d Planar / DC) in %d entries" % (leaves.size, n_regular, items.size))
     lines += ["", "x copy: prediction time / mip_copy_device of the same number of output bytes;",
               "x search/fr: prediction time per frame of the case / search time per frame."]
     text = "\n".join(lines) + "\n"

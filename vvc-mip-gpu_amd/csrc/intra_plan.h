@@ -1,8 +1,10 @@
 // intra_plan.h -- the Planar / DC baseline costs (include/mipgpu.h, mip_intra_device) as
 // per-sample and per-4x4-block arithmetic, shared by the kernel (mip_intra.hip: one lane per
 // 4x4 block) and by the host restatement below (intra_frames_host: the same steps, one CU at
-// a time), plus the lane-slot lists the kernel walks and the decision merge.  No HIP
-// dependency on the host side; unit-tested by tests/cpp/test_intra_plan.cpp.
+// a time), plus the lane-slot lists the kernel walks and the decision merge.  The per-sample
+// functions also build the Planar / DC blocks that the prediction kernel emits (mip_predict.hip)
+// and their host restatement (intra_predict_cu_host).  No HIP dependency on the host side;
+// unit-tested by tests/cpp/test_intra_plan.cpp and tests/cpp/test_intra_predict.cpp.
 //
 // A "Ref" is any callable ref(row, col) -> reference sample at frame row / column, read by
 // linear index row * W + col like everything else here: global memory on the host, the staged
@@ -239,6 +241,29 @@ inline void intra_cu_host(const uint16_t *orig, const uint16_t *refs, int width,
       const IntraSums s = intra_block(b, org);
       for (int m = 0; m < kIntraModes; m++) sad[m] += s.sad[m], satd[m] += s.satd[m];
     }
+}
+
+// The samples of one CU (mip_predict_device_ex with MIP_PRED_REGULAR): the Planar
+// (MIP_MODE_PLANAR) or DC (MIP_MODE_DC) block of the w x h CU at frame position (x, y) after PDPC,
+// row r at out[r * pitch .. + w).  refs is one frame; the steps are the prediction kernel's
+// (mip_predict.hip store_regular).  Returns 0, or -1 for any other mode (nothing written).
+inline int intra_predict_cu_host(const uint16_t *refs, int width, int x, int y, int lw, int lh, int mode, uint16_t *out,
+                                 int pitch) {
+  if (mode != MIP_MODE_PLANAR && mode != MIP_MODE_DC) return -1;
+  const IntraHostRef ref{refs, width};
+  const int w = 1 << lw, h = 1 << lh, scale = (lw + lh - 2) >> 2;
+  int top[64], left[64], sum_top = 0, sum_left = 0;
+  for (int i = 0; i < w; i++) sum_top += top[i] = intra_top(ref, x, y, i);
+  for (int j = 0; j < h; j++) sum_left += left[j] = intra_left(ref, x, y, j);
+  const int tr = top[w - 1], bl = left[h - 1], dc = intra_dc(sum_top, sum_left, lw, lh);
+  for (int j = 0; j < h; j++) {
+    const int wt = intra_pdpc_weight(j, scale);
+    for (int i = 0; i < w; i++) {
+      const int p = mode == MIP_MODE_PLANAR ? intra_planar(top[i], left[j], tr, bl, i, j, lw, lh) : dc;
+      out[(size_t)j * pitch + i] = (uint16_t)intra_pdpc(p, top[i], left[j], wt, intra_pdpc_weight(i, scale));
+    }
+  }
+  return 0;
 }
 
 // The tables of mip_intra_device on host arrays (each optional): frames / refs

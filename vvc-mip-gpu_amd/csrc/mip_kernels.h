@@ -177,6 +177,8 @@ struct PredictArgs {
   uint32_t *skipped;          // optional: items that were not written are counted here
   int width, height, ctu_cols, nctus, nframes;
   int refs_vec;               // refs is 8-byte aligned: top rows are read 4 samples per load
+  int regular;                // MIP_PRED_REGULAR: items with mode MIP_MODE_PLANAR / MIP_MODE_DC are emitted
+                              // (launches the kernel's second instance; 0: the MIP-only one)
 };
 hipError_t launch_predict(const PredictArgs &a, hipStream_t s);
 

@@ -19,10 +19,18 @@
 // row from the anchor rows (the vertical pass needs no second buffer) and stores them with
 // one 16-byte (8-byte) store.  All LDS traffic is wave-private: no workgroup barrier.
 //
+// Regular items (the kernel's second instance, MIP_PRED_REGULAR): an item whose mode is
+// MIP_MODE_PLANAR / MIP_MODE_DC needs the boundaries and, for DC, their two sums (eight partial
+// sums in red[], where a MIP item keeps its reduced boundaries); it idles through the GEMV and
+// anchor-row phases of its MIP neighbours and builds its samples in the store phase with the
+// per-sample functions of intra_plan.h -- the text the cost kernel (mip_intra.hip) and the host
+// restatement run, so an emitted block is the one whose SAD / SATD mip_intra_device reports.
+//
 // Every item is checked here against the write rule of include/mipgpu.h (the list is data
 // in device memory): a bad entry writes nothing, reads no sample and is counted.
 #include <algorithm>
 
+#include "intra_plan.h"
 #include "mip_kernels.h"
 #include "mip_tables.h"
 
@@ -39,7 +47,7 @@ constexpr int kPredItemsPerWave = 4;   // list items a wave takes at a time (one
 // Wave-private LDS words.  A group of G lanes (64: the wave, 16: a quarter) keeps
 //   top[G] left[G] red[8] rpred[G] anchor[r x w]
 // (anchor rows: r x w <= 8 x 64 for the wave, 4 x 16 for a quarter); every array starts on a
-// 16-byte boundary.
+// 16-byte boundary.  A regular item uses top, left and red only.
 constexpr int lds_words(int g) { return 3 * g + 8 + (g == 64 ? 8 * 64 : 4 * 16); }
 constexpr int kWaveWords = lds_words(64);  // 712
 constexpr int kGroupWords = 176;           // a quarter's words (120 used), 16-byte aligned
@@ -56,9 +64,10 @@ __device__ __forceinline__ void wave_lds_sync() {
 
 __device__ __forceinline__ int ilog2i(int v) { return 31 - __clz(v); }
 
-// One list item, decoded and checked: on = it is written.
+// One list item, decoded and checked: on = it is written, reg = a regular (Planar / DC) item,
+// only ever set in the kernel's MIP_PRED_REGULAR instance.
 struct Item {
-  bool on;
+  bool on, reg;
   int frame, x, y, w, h, sid, modes, mode, pitch;
   long long offset;
 };
@@ -102,13 +111,52 @@ __device__ __forceinline__ void store_rows(const Item &c, const int *top, const 
   }
 }
 
+// The same lane units for a regular item: Planar or DC, then PDPC (include/mipgpu.h,
+// mip_intra_device), from the boundaries and the eight partial sums in red[].
+template <int V>
+__device__ __forceinline__ void store_regular(const Item &c, const int *top, const int *left, const int *red, int t, int step,
+                                              uint16_t *out) {
+  const int w = c.w, lw = ilog2i(w), lh = ilog2i(c.h), scale = (lw + lh - 2) >> 2;
+  const int lu = lw - (V == 8 ? 3 : 2);
+  const int units = (c.h * w) >> (V == 8 ? 3 : 2);
+  const bool planar = c.mode == MIP_MODE_PLANAR;
+  const int4 st = *reinterpret_cast<const int4 *>(red), sl = *reinterpret_cast<const int4 *>(red + 4);
+  const int dc = intra_dc(st.x + st.y + st.z + st.w, sl.x + sl.y + sl.z + sl.w, lw, lh);
+  const int tr = top[w - 1], bl = left[c.h - 1];
+  for (int u = t; u < units; u += step) {
+    const int yy = u >> lu, xx = (u & ((1 << lu) - 1)) * V;
+    const int lj = left[yy], wt = intra_pdpc_weight(yy, scale);
+    int v[V];
+#pragma unroll
+    for (int q = 0; q < V; q += 4) {
+      const int4 tf = *reinterpret_cast<const int4 *>(top + xx + q);
+      const int ti[4] = {tf.x, tf.y, tf.z, tf.w};
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const int i = xx + q + k;
+        const int p = planar ? intra_planar(ti[k], lj, tr, bl, i, yy, lw, lh) : dc;
+        v[q + k] = intra_pdpc(p, ti[k], lj, wt, intra_pdpc_weight(i, scale));
+      }
+    }
+    uint16_t *dst = out + c.offset + (long long)yy * c.pitch + xx;
+    if constexpr (V == 8) {
+      *reinterpret_cast<uint4 *>(dst) = make_uint4((uint32_t)v[0] | (uint32_t)v[1] << 16, (uint32_t)v[2] | (uint32_t)v[3] << 16,
+                                                   (uint32_t)v[4] | (uint32_t)v[5] << 16, (uint32_t)v[6] | (uint32_t)v[7] << 16);
+    } else {
+      *reinterpret_cast<uint2 *>(dst) = make_uint2((uint32_t)v[0] | (uint32_t)v[1] << 16, (uint32_t)v[2] | (uint32_t)v[3] << 16);
+    }
+  }
+}
+
 // Prediction of one item by a group of G lanes (t = lane inside the group, L = the group's
 // LDS words).  Called by whole waves: lanes of groups without an item to write run it with
-// c.on = false (no memory access), so that the fences sit in wave-uniform control flow.
-template <int G>
+// c.on = false (no memory access), so that the fences sit in wave-uniform control flow.  For the
+// same reason a regular item's group runs every phase: mip = false predicates the MIP steps.
+template <int G, bool REGULAR>
 __device__ __forceinline__ void predict_cu(const PredictArgs &a, const Item &c, int t, int *L) {
   int *top = L, *left = L + G, *red = L + 2 * G, *rpred = L + 2 * G + 8, *anc = L + 3 * G + 8;
   const int W = a.width, w = c.w, h = c.h, x = c.x, y = c.y, sid = c.sid;
+  const bool reg = REGULAR && c.reg, mip = c.on && !reg;
   const uint16_t *F = a.refs + (size_t)c.frame * W * a.height;
   // complete boundaries (linear indexes, intra.cl:100, 106, 236, 242)
   if (c.on) {
@@ -129,18 +177,18 @@ __device__ __forceinline__ void predict_cu(const PredictArgs &a, const Item &c, 
     if (t < h) left[t] = x > 0 ? F[(size_t)(y + t) * W + x - 1] : (y == 0 ? 512 : F[(size_t)(y - 1) * W]);
   }
   wave_lds_sync();
-  const int rbs = sid == 0 ? 2 : 4;
+  const int rbs = sid == 0 && !reg ? 2 : 4;
   if (c.on && t < 2 * rbs) {  // reduced boundaries: box averages; a factor of 1 is a copy
     const int side = t >= rbs, i = t - side * rbs, len = side ? h : w, df = len / rbs, l2 = ilog2i(df);
     const int rnd = df > 1 ? 1 << (l2 - 1) : 0;
     const int *src = side ? left : top;
     int s = 0;
     for (int k = 0; k < df; k++) s += src[i * df + k];
-    red[side * 4 + i] = (s + rnd) >> l2;
+    red[side * 4 + i] = reg ? s : (s + rnd) >> l2;  // (a regular item: quarter sums for DC)
   }
   wave_lds_sync();
   const int r = sid == 2 ? 8 : 4, lr = sid == 2 ? 3 : 2;
-  if (c.on && t < r * r) {  // reduced prediction (intra.cl:415-485), one output per lane
+  if (mip && t < r * r) {  // reduced prediction (intra.cl:415-485), one output per lane
     const bool tr = c.mode >= c.modes;
     const int mode = tr ? c.mode - c.modes : c.mode;
     const int4 rt = *reinterpret_cast<const int4 *>(red), rl = *reinterpret_cast<const int4 *>(red + 4);
@@ -176,7 +224,7 @@ __device__ __forceinline__ void predict_cu(const PredictArgs &a, const Item &c, 
     rpred[tr ? ((t & (r - 1)) << lr) + (t >> lr) : t] = v;
   }
   wave_lds_sync();
-  if (c.on) {  // horizontal pass on the anchor rows (a factor of 1 is a copy): anc[k][xx]
+  if (mip) {  // horizontal pass on the anchor rows (a factor of 1 is a copy): anc[k][xx]
     const int uh = w >> lr, uv = h >> lr, lh = ilog2i(uh), lw = ilog2i(w);
     for (int i = t; i < r * w; i += G) {
       const int k = i >> lw, xx = i & (w - 1);
@@ -195,16 +243,23 @@ __device__ __forceinline__ void predict_cu(const PredictArgs &a, const Item &c, 
   if (c.on) {
     // 16-byte stores where every row segment of the block is 16-byte aligned
     const bool wide = w >= 8 && (c.pitch & 7) == 0 && ((reinterpret_cast<uintptr_t>(a.out + c.offset) & 15) == 0);
-    if (wide) store_rows<8>(c, top, anc, t, G, a.out);
-    else store_rows<4>(c, top, anc, t, G, a.out);
+    if (reg) {
+      if (wide) store_regular<8>(c, top, left, red, t, G, a.out);
+      else store_regular<4>(c, top, left, red, t, G, a.out);
+    } else if (wide) {
+      store_rows<8>(c, top, anc, t, G, a.out);
+    } else {
+      store_rows<4>(c, top, anc, t, G, a.out);
+    }
   }
   wave_lds_sync();  // the next item rewrites the group's words
 }
 
 // The write rule of include/mipgpu.h, item by item.
+template <bool REGULAR>
 __device__ __forceinline__ Item decode(const PredictArgs &a, const mip_pred_item &it) {
   Item c{};
-  c.on = false;
+  c.on = c.reg = false;
   if (it.frame < 0 || it.frame >= a.nframes || it.cu < 0 || it.cu >= a.nctus * MIP_CUS_PER_CTU) return c;
   if (a.unavail[it.cu]) return c;
   const int ctu = it.cu / MIP_CUS_PER_CTU;
@@ -214,7 +269,8 @@ __device__ __forceinline__ Item decode(const PredictArgs &a, const mip_pred_item
   c.h = sd.h;
   c.sid = sd.size_id;
   c.modes = sd.modes;
-  if (it.mode < 0 || it.mode >= 2 * c.modes) return c;
+  const bool reg = REGULAR && (it.mode == MIP_MODE_PLANAR || it.mode == MIP_MODE_DC);  // every shape has both
+  if (!reg && (it.mode < 0 || it.mode >= 2 * c.modes)) return c;
   if (it.pitch < c.w || (it.pitch & 3) || (it.offset & 3) || it.offset < 0 || it.offset > a.out_samples) return c;
   if (a.out_samples - it.offset < (long long)(c.h - 1) * it.pitch + c.w) return c;
   c.frame = it.frame;
@@ -223,12 +279,14 @@ __device__ __forceinline__ Item decode(const PredictArgs &a, const mip_pred_item
   c.mode = it.mode;
   c.pitch = it.pitch;
   c.offset = it.offset;
+  c.reg = reg;
   c.on = true;
   return c;
 }
 
 __device__ __forceinline__ int bcast(int v, int src) { return __builtin_amdgcn_readfirstlane(__shfl(v, src, 64)); }
 
+template <bool REGULAR>
 __global__ __launch_bounds__(64 * kPredWaves) void predict_kernel(PredictArgs a) {
   __shared__ __attribute__((aligned(16))) int lds[kPredWaves * kWaveWords];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, grp = lane >> 4;
@@ -237,20 +295,21 @@ __global__ __launch_bounds__(64 * kPredWaves) void predict_kernel(PredictArgs a)
   for (long long q = (long long)blockIdx.x * kPredWaves + wv; q < quads; q += (long long)gridDim.x * kPredWaves) {
     const long long idx = q * kPredItemsPerWave + grp;  // the 16-lane group's item
     Item c{};
-    c.on = false;
+    c.on = c.reg = false;
     if (idx < a.n) {
-      c = decode(a, a.items[idx]);
+      c = decode<REGULAR>(a, a.items[idx]);
       if (!c.on && (lane & 15) == 0 && a.skipped) atomicAdd(a.skipped, 1u);
     }
     const bool large = c.on && c.w * c.h > 64;
     if (!__any(large)) {
-      predict_cu<16>(a, c, lane & 15, wl + grp * kGroupWords);
+      predict_cu<16, REGULAR>(a, c, lane & 15, wl + grp * kGroupWords);
     } else {
       for (int j = 0; j < kPredItemsPerWave; j++) {
         const int src = 16 * j;
         if (!bcast(c.on, src)) continue;  // wave-uniform
         Item u;
         u.on = true;
+        u.reg = REGULAR && bcast(c.reg, src);
         u.frame = bcast(c.frame, src);
         u.x = bcast(c.x, src);
         u.y = bcast(c.y, src);
@@ -262,7 +321,7 @@ __global__ __launch_bounds__(64 * kPredWaves) void predict_kernel(PredictArgs a)
         u.pitch = bcast(c.pitch, src);
         const uint32_t lo = (uint32_t)bcast((int)(uint32_t)c.offset, src), hi = (uint32_t)bcast((int)(c.offset >> 32), src);
         u.offset = (long long)(((unsigned long long)hi << 32) | lo);
-        predict_cu<64>(a, u, lane, wl);
+        predict_cu<64, REGULAR>(a, u, lane, wl);
       }
     }
   }
@@ -276,7 +335,9 @@ hipError_t launch_predict(const PredictArgs &a, hipStream_t s) {
   // grid-stride over the list: 16 items per workgroup pass, at most 16 workgroups per CU's worth
   const long long per_group = (long long)kPredWaves * kPredItemsPerWave;
   const long long groups = std::min<long long>((a.n + per_group - 1) / per_group, 256 * 16);
-  hipLaunchKernelGGL(predict_kernel, dim3((unsigned)groups), dim3(64 * kPredWaves), 0, s, a);
+  // (flags 0 runs the MIP-only instance: no regular-item code in it)
+  if (a.regular) hipLaunchKernelGGL(predict_kernel<true>, dim3((unsigned)groups), dim3(64 * kPredWaves), 0, s, a);
+  else hipLaunchKernelGGL(predict_kernel<false>, dim3((unsigned)groups), dim3(64 * kPredWaves), 0, s, a);
   return hipGetLastError();
 }
 

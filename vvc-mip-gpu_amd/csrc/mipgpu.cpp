@@ -957,7 +957,7 @@ static int ensure_pred_tables(mip_engine *e) {
 // refs: the reference frames to predict from (already resolved); engine_refs: they are the
 // engine filter's output (its unavailable set applies).
 static int predict_launch(mip_engine *e, const uint16_t *refs, bool engine_refs, int nframes, const mip_pred_item *d_items,
-                          int64_t n, uint16_t *d_out, int64_t out_samples, uint32_t *d_skipped, hipStream_t s) {
+                          int64_t n, uint16_t *d_out, int64_t out_samples, uint32_t *d_skipped, unsigned flags, hipStream_t s) {
   mipgpu::PredictArgs a{};
   a.refs = refs;
   a.items = d_items;
@@ -973,12 +973,14 @@ static int predict_launch(mip_engine *e, const uint16_t *refs, bool engine_refs,
   a.nctus = e->nctus;
   a.nframes = nframes;
   a.refs_vec = (reinterpret_cast<uintptr_t>(refs) & 7) == 0;
+  a.regular = (flags & MIP_PRED_REGULAR) != 0;
   HIP_TRY(mipgpu::launch_predict(a, s));
   return 0;
 }
 
 static int predict_args_ok(const mip_engine *e, int nframes, const void *items, int64_t n, const void *out,
-                           int64_t out_samples) {
+                           int64_t out_samples, unsigned flags) {
+  if (flags & ~MIP_PRED_REGULAR) return fail("unknown prediction flags 0x%x", flags);
   if (nframes < 1 || n < 0 || out_samples < 0 || (n && (!items || !out))) return fail("bad prediction arguments");
   if (n > kMaxCus) return fail("%lld prediction items exceed %lld per call", (long long)n, kMaxCus);
   if ((long long)nframes * e->nctus * MIP_CUS_PER_CTU > kMaxCus) return fail("%d frames exceed %lld CUs per call", nframes, kMaxCus);
@@ -988,10 +990,16 @@ static int predict_args_ok(const mip_engine *e, int nframes, const void *items, 
 int mip_predict_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes,
                        const mip_pred_item *d_items, int64_t n, uint16_t *d_out, int64_t out_samples,
                        uint32_t *d_skipped, void *stream) {
+  return mip_predict_device_ex(e, d_frames, d_refs, nframes, d_items, n, d_out, out_samples, d_skipped, 0, stream);
+}
+
+int mip_predict_device_ex(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes,
+                          const mip_pred_item *d_items, int64_t n, uint16_t *d_out, int64_t out_samples,
+                          uint32_t *d_skipped, unsigned flags, void *stream) {
   if (!e) return fail("engine is NULL");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   if (!d_frames && !d_refs) return fail("bad prediction arguments: no frames");
-  if (predict_args_ok(e, nframes, d_items, n, d_out, out_samples) != 0) return -1;
+  if (predict_args_ok(e, nframes, d_items, n, d_out, out_samples, flags) != 0) return -1;
   if ((reinterpret_cast<uintptr_t>(d_out) & 7) || (reinterpret_cast<uintptr_t>(d_items) & 7))
     return fail("d_out and d_items must be 8-byte aligned");
   if (n == 0) return 0;
@@ -1010,7 +1018,7 @@ int mip_predict_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *
       return -1;
     refs = e->d_refs;
   }
-  if (predict_launch(e, refs, engine_refs, nframes, d_items, n, d_out, out_samples, d_skipped, s) != 0) return -1;
+  if (predict_launch(e, refs, engine_refs, nframes, d_items, n, d_out, out_samples, d_skipped, flags, s) != 0) return -1;
   if (engine_refs) {
     HIP_TRY(hipEventRecord(e->refs_done, s));
     e->refs_pending = true;
@@ -1020,10 +1028,16 @@ int mip_predict_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *
 
 int mip_predict_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
                        const mip_pred_item *items, int64_t n, uint16_t *out, int64_t out_samples, int64_t *skipped) {
+  return mip_predict_frames_ex(e, frames, refs_or_null, nframes, items, n, out, out_samples, 0, skipped);
+}
+
+int mip_predict_frames_ex(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
+                          const mip_pred_item *items, int64_t n, uint16_t *out, int64_t out_samples, unsigned flags,
+                          int64_t *skipped) {
   if (!e) return fail("engine is NULL");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   if (!frames && !refs_or_null) return fail("bad prediction arguments: no frames");
-  if (predict_args_ok(e, nframes, items, n, out, out_samples) != 0) return -1;
+  if (predict_args_ok(e, nframes, items, n, out, out_samples, flags) != 0) return -1;
   if (out_samples && !out) return fail("bad prediction arguments: out is NULL");
   // the list on the host: names outside the call's frames / the frame's CUs are the caller's bug
   for (int64_t i = 0; i < n; i++) {
@@ -1084,7 +1098,7 @@ int mip_predict_frames(mip_engine *e, const uint16_t *frames, const uint16_t *re
     }
     refs = d_refs;
   }
-  if (predict_launch(e, refs, engine_refs, nframes, d_items, n, d_out, out_samples, d_skip, s) != 0) return done(-1);
+  if (predict_launch(e, refs, engine_refs, nframes, d_items, n, d_out, out_samples, d_skip, flags, s) != 0) return done(-1);
   uint32_t nskip = 0;
   PRED_TRY(hipMemcpyAsync(out, d_out, (size_t)out_samples * 2, hipMemcpyDeviceToHost, s));
   PRED_TRY(hipMemcpyAsync(&nskip, d_skip, sizeof nskip, hipMemcpyDeviceToHost, s));
@@ -1192,6 +1206,93 @@ int mip_partition_frames(mip_engine *e, const uint16_t *frames, const uint16_t *
 #undef PART_TRY
   e->refs_pending = false;
   if (const uint32_t f = take_status(e, mip_engine::kCallRing)) return done(contract_error(f, "mip_partition_frames"));
+  return done(0);
+}
+
+// The whole device chain on host frames: decisions, Planar / DC merge, partition and the
+// partition's predicted frames, chunk by chunk like mip_partition_frames.
+int mip_predicted_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
+                         const int32_t *penalty, const int32_t *bias, uint8_t *best_mode_out, int32_t *best_cost_out,
+                         uint8_t *leaf_out, int32_t *ctu_cost_out, int32_t *ctu_leaves_out, uint16_t *pred_out) {
+  if (!e) return fail("engine is NULL");
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (!frames) return fail("bad partition arguments: no frames");
+  if (partition_args_ok(e->width, e->height, nframes, penalty,
+                        best_mode_out || best_cost_out || leaf_out || ctu_cost_out || ctu_leaves_out || pred_out) != 0)
+    return -1;
+  if (!mipgpu::intra_bias_ok(bias)) return fail("intra: a bias is outside 0..%d", (int)mipgpu::kIntraMaxBias);
+  if (e->opts.best_k != 1) return fail("mip_predicted_frames needs best_k <= 1 (got %d)", e->opts.best_k);
+  HIP_TRY(hipSetDevice(e->device));
+  if (quiesce(e) != 0) return -1;  // (host searches in flight use the engine buffers)
+  if (check_device_status(e) != 0) return -1;  // (an earlier device-API search's violation)
+  if (ensure_pred_tables(e) != 0) return -1;
+  const size_t fs = (size_t)e->width * e->height, ncu = (size_t)e->nctus * MIP_CUS_PER_CTU, mb = (size_t)e->opts.max_batch;
+  const size_t chunk = std::min(mb, (size_t)nframes), per_frame = (size_t)e->nctus * MIP_PART_MAX_LEAVES;  // list entries
+  if (!e->d_part_leaf) HIP_TRY(dev_malloc(e->device, (void **)&e->d_part_leaf, mb * ncu));
+  if (!e->d_part_ctu) HIP_TRY(dev_malloc(e->device, (void **)&e->d_part_ctu, mb * e->nctus * 2 * sizeof(int32_t)));
+  // the call's own device buffers (through the device block cache): caller references on an
+  // engine without a reference buffer, one chunk's item list and its frame canvases
+  uint16_t *t_refs = nullptr, *d_pred = nullptr;
+  mip_pred_item *d_items = nullptr;
+  auto done = [&](int rc) {
+    for (void *p : {(void *)t_refs, (void *)d_pred, (void *)d_items}) dev_free(p);
+    return rc;
+  };
+#define CHAIN_TRY(expr)                                                                    \
+  do {                                                                                     \
+    hipError_t _e = (expr);                                                                \
+    if (_e != hipSuccess) return done(fail("%s: %s", #expr, hipGetErrorString(_e)));       \
+  } while (0)
+  uint16_t *d_refs = nullptr;
+  if (refs_or_null) {
+    d_refs = e->d_refs;
+    if (!d_refs) {
+      CHAIN_TRY(dev_malloc(e->device, (void **)&t_refs, mb * fs * 2));
+      d_refs = t_refs;
+    }
+  }
+  if (pred_out) {
+    CHAIN_TRY(dev_malloc(e->device, (void **)&d_items, chunk * per_frame * sizeof(mip_pred_item)));
+    CHAIN_TRY(dev_malloc(e->device, (void **)&d_pred, chunk * fs * 2));
+  }
+  const bool engine_refs = !refs_or_null && e->opts.filter != MIP_FILTER_NONE;
+  hipStream_t s = e->stream;
+  int32_t *d_ctu_cost = e->d_part_ctu, *d_ctu_leaves = e->d_part_ctu + mb * e->nctus;
+  for (int f0 = 0; f0 < nframes; f0 += e->opts.max_batch) {
+    const size_t nb = (size_t)std::min(e->opts.max_batch, nframes - f0);
+    CHAIN_TRY(hipMemcpyAsync(e->d_frames, frames + f0 * fs, nb * fs * 2, hipMemcpyHostToDevice, s));
+    if (d_refs) CHAIN_TRY(hipMemcpyAsync(d_refs, refs_or_null + f0 * fs, nb * fs * 2, hipMemcpyHostToDevice, s));
+    // (without references the search filters the frames into e->d_refs when the engine has a
+    // filter; the merge and the prediction below read that buffer)
+    if (search_device_impl(e, e->d_frames, d_refs, (int)nb, nullptr, nullptr, nullptr, e->d_best, e->d_best_cost, s,
+                           d_refs != nullptr, device_status(e)) != 0)
+      return done(-1);
+    if (mip_intra_device(e, e->d_frames, d_refs, (int)nb, nullptr, nullptr, nullptr, bias, e->d_best, e->d_best_cost, s) != 0)
+      return done(-1);
+    // the list's frame indexes and offsets are the chunk's own: 0 .. nb-1 into d_pred
+    if (mip_partition_device(e->d_best_cost, e->d_best, e->width, e->height, (int)nb, penalty, e->d_part_leaf, d_ctu_cost,
+                             d_ctu_leaves, d_items, s) != 0)
+      return done(-1);
+    if (pred_out) {
+      CHAIN_TRY(hipMemsetAsync(d_pred, 0xff, nb * fs * 2, s));  // MIP_PRED_NONE
+      const uint16_t *refs = d_refs ? d_refs : engine_refs ? e->d_refs : e->d_frames;
+      if (predict_launch(e, refs, engine_refs, (int)nb, d_items, (int64_t)(nb * per_frame), d_pred, (int64_t)(nb * fs), nullptr,
+                         MIP_PRED_REGULAR, s) != 0)
+        return done(-1);
+      CHAIN_TRY(hipMemcpyAsync(pred_out + f0 * fs, d_pred, nb * fs * 2, hipMemcpyDeviceToHost, s));
+    }
+    if (best_mode_out) CHAIN_TRY(hipMemcpyAsync(best_mode_out + f0 * ncu, e->d_best, nb * ncu, hipMemcpyDeviceToHost, s));
+    if (best_cost_out) CHAIN_TRY(hipMemcpyAsync(best_cost_out + f0 * ncu, e->d_best_cost, nb * ncu * 4, hipMemcpyDeviceToHost, s));
+    if (leaf_out) CHAIN_TRY(hipMemcpyAsync(leaf_out + f0 * ncu, e->d_part_leaf, nb * ncu, hipMemcpyDeviceToHost, s));
+    if (ctu_cost_out)
+      CHAIN_TRY(hipMemcpyAsync(ctu_cost_out + (size_t)f0 * e->nctus, d_ctu_cost, nb * e->nctus * 4, hipMemcpyDeviceToHost, s));
+    if (ctu_leaves_out)
+      CHAIN_TRY(hipMemcpyAsync(ctu_leaves_out + (size_t)f0 * e->nctus, d_ctu_leaves, nb * e->nctus * 4, hipMemcpyDeviceToHost, s));
+    CHAIN_TRY(hipStreamSynchronize(s));
+  }
+#undef CHAIN_TRY
+  e->refs_pending = false;
+  if (const uint32_t f = take_status(e, mip_engine::kCallRing)) return done(contract_error(f, "mip_predicted_frames"));
   return done(0);
 }
 

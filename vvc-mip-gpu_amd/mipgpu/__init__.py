@@ -64,6 +64,7 @@ PART_MAX_PENALTY = 1 << 20                 # per-shape penalties of the partitio
 MODE_PLANAR = 0xF0                         # MIP_MODE_PLANAR / MIP_MODE_DC: best_mode values written by the
 MODE_DC = 0xF1                             # merge of intra_device (regular intra modes, not MIP modes)
 INTRA_MAX_BIAS = 1 << 20                   # biases of that merge: 0 .. 1<<20
+PRED_REGULAR = 1                           # MIP_PRED_REGULAR: flags bit of predict(..., regular=True)
 
 
 class _Opts(ctypes.Structure):
@@ -145,6 +146,9 @@ def library():
         "mip_pred_layout": (ip, [ip, ip, ip, ip, vp, i64, ctypes.POINTER(i64)]),
         "mip_predict_device": (ip, [vp, vp, vp, ip, vp, i64, vp, i64, vp, vp]),
         "mip_predict_frames": (ip, [vp, vp, vp, ip, vp, i64, vp, i64, ctypes.POINTER(i64)]),
+        "mip_predict_device_ex": (ip, [vp, vp, vp, ip, vp, i64, vp, i64, vp, ctypes.c_uint, vp]),
+        "mip_predict_frames_ex": (ip, [vp, vp, vp, ip, vp, i64, vp, i64, ctypes.c_uint, ctypes.POINTER(i64)]),
+        "mip_predicted_frames": (ip, [vp, vp, vp, ip, vp, vp, vp, vp, vp, vp, vp, vp]),
         "mip_partition_device": (ip, [vp, vp, ip, ip, ip, vp, vp, vp, vp, vp, vp]),
         "mip_partition_frames": (ip, [vp, vp, vp, ip, vp, vp, vp, vp, vp, vp]),
         "mip_intra_device": (ip, [vp, vp, vp, ip, vp, vp, vp, vp, vp, vp, vp]),
@@ -434,37 +438,73 @@ class MipEngine:
             _check(library().mip_check_input(self._h, ctypes.c_void_p(s.cuda_stream)))
 
     # ------------------------------------------------------- prediction output
-    def predict(self, frames, items, out_samples, refs=None):
+    def predict(self, frames, items, out_samples, refs=None, regular=False):
         """Predicted samples of the list `items` (PRED_ITEM array, see pred_items) for host
         frames (mip_predict_frames).  Returns (uint16 array of out_samples, skipped): samples
         no item wrote are PRED_NONE; skipped counts the items that were not written
-        (unavailable CUs, mode "none", blocks that do not fit)."""
+        (unavailable CUs, mode "none", blocks that do not fit).  regular=True
+        (mip_predict_frames_ex, MIP_PRED_REGULAR): items with mode MODE_PLANAR / MODE_DC are
+        emitted too -- the Planar / DC blocks whose costs intra() reports."""
         f = self._frames(frames)
         r = None if refs is None else self._frames(refs)
         it = np.ascontiguousarray(items, dtype=PRED_ITEM)
         out = np.empty(int(out_samples), np.uint16)
         skipped = ctypes.c_int64()
         with self._lock:
-            _check(library().mip_predict_frames(self._h, _ptr(f), _ptr(r), f.shape[0], _ptr(it), it.size, _ptr(out),
-                                                int(out_samples), ctypes.byref(skipped)))
+            if regular:
+                _check(library().mip_predict_frames_ex(self._h, _ptr(f), _ptr(r), f.shape[0], _ptr(it), it.size, _ptr(out),
+                                                       int(out_samples), PRED_REGULAR, ctypes.byref(skipped)))
+            else:
+                _check(library().mip_predict_frames(self._h, _ptr(f), _ptr(r), f.shape[0], _ptr(it), it.size, _ptr(out),
+                                                    int(out_samples), ctypes.byref(skipped)))
         return out, int(skipped.value)
 
-    def predict_device(self, frames, items, out, refs=None, skipped=None, stream=None):
+    def predict_device(self, frames, items, out, refs=None, skipped=None, stream=None, regular=False):
         """Asynchronous prediction on device tensors (mip_predict_device): `items` is a uint8
         tensor of the PRED_ITEM bytes (torch.from_numpy(items.view(np.uint8)).cuda()), `out` a
         uint16 / int16 tensor the blocks are written into (other samples are left as they are),
         `skipped` an optional zeroed int32 tensor of one element that counts the items not
-        written.  Returns `out`."""
+        written.  regular=True (mip_predict_device_ex, MIP_PRED_REGULAR): items with mode
+        MODE_PLANAR / MODE_DC are emitted too, so the item list of partition_device on merged
+        decisions gives whole predicted frames.  Returns `out`."""
         import torch
         nbytes = items.numel() * items.element_size()
         if nbytes % PRED_ITEM.itemsize:
             raise MipError("predict_device: items is not a whole number of %d-byte entries" % PRED_ITEM.itemsize)
         s = stream if stream is not None else torch.cuda.current_stream(frames.device)
         with self._lock:
-            _check(library().mip_predict_device(self._h, _ptr(frames), _ptr(refs), frames.shape[0], _ptr(items),
-                                                nbytes // PRED_ITEM.itemsize, _ptr(out), out.numel(), _ptr(skipped),
-                                                ctypes.c_void_p(s.cuda_stream)))
+            if regular:
+                _check(library().mip_predict_device_ex(self._h, _ptr(frames), _ptr(refs), frames.shape[0], _ptr(items),
+                                                       nbytes // PRED_ITEM.itemsize, _ptr(out), out.numel(), _ptr(skipped),
+                                                       PRED_REGULAR, ctypes.c_void_p(s.cuda_stream)))
+            else:
+                _check(library().mip_predict_device(self._h, _ptr(frames), _ptr(refs), frames.shape[0], _ptr(items),
+                                                    nbytes // PRED_ITEM.itemsize, _ptr(out), out.numel(), _ptr(skipped),
+                                                    ctypes.c_void_p(s.cuda_stream)))
         return out
+
+    def predicted_frames(self, frames, penalty=None, bias=None, refs=None) -> dict:
+        """The whole chain on host frames (mip_predicted_frames; needs best_k = 1): decisions,
+        Planar / DC merge with `bias` (see intra_device), CTU partition with `penalty` (see
+        partition_device) and the partition's predicted frames.  dict of numpy arrays: 'best_mode'
+        uint8 / 'best_cost' int32 (the merged decisions) / 'leaf' uint8 [F, nCTUs*5380], 'ctu_cost'
+        / 'ctu_leaves' int32 [F, nCTUs] and 'pred' uint16 [F, H, W] -- every leaf's MIP, Planar or
+        DC block at its place, PRED_NONE where no leaf is (CTUs without a partition)."""
+        f = self._frames(frames)
+        r = None if refs is None else self._frames(refs)
+        n = f.shape[0]
+        pen, b = _penalty(penalty), _bias(bias)
+        res = {"best_mode": np.empty((n, self.cus_per_frame), np.uint8),
+               "best_cost": np.empty((n, self.cus_per_frame), np.int32),
+               "leaf": np.empty((n, self.cus_per_frame), np.uint8),
+               "ctu_cost": np.empty((n, self.nctus), np.int32),
+               "ctu_leaves": np.empty((n, self.nctus), np.int32),
+               "pred": np.empty((n, self.height, self.width), np.uint16)}
+        with self._lock:
+            _check(library().mip_predicted_frames(self._h, _ptr(f), _ptr(r), n, _ptr(pen), _ptr(b), _ptr(res["best_mode"]),
+                                                  _ptr(res["best_cost"]), _ptr(res["leaf"]), _ptr(res["ctu_cost"]),
+                                                  _ptr(res["ctu_leaves"]), _ptr(res["pred"])))
+        return res
 
     # ------------------------------------------------------- partition decision
     def partition(self, frames, penalty=None, refs=None) -> dict:
@@ -666,6 +706,6 @@ def filter_device(frames_in, frames_out, filter, kernel_idx=0, stream=None):
     return frames_out
 
 
-__all__ = ["MODE_PLANAR", "MODE_DC", "INTRA_MAX_BIAS", "PRED_ITEM", "PRED_NONE", "pred_items", "PART_MAX_LEAVES", "PART_MAX_PENALTY", "partition_device", "MipEngine", "MipError", "build_id", "source_id", "FILTERS", "FILTER_NONE", "filter_index", "filter_device", "topk_device", "library",
+__all__ = ["MODE_PLANAR", "MODE_DC", "INTRA_MAX_BIAS", "PRED_REGULAR", "PRED_ITEM", "PRED_NONE", "pred_items", "PART_MAX_LEAVES", "PART_MAX_PENALTY", "partition_device", "MipEngine", "MipError", "build_id", "source_id", "FILTERS", "FILTER_NONE", "filter_index", "filter_device", "topk_device", "library",
            "pinned_empty", "unavailable_cus", "numa_node", "bind_thread", "device_cache", "copy_device",
            "layout", "SHAPES", "COSTS_PER_CTU", "CUS_PER_CTU", "UNAVAILABLE", "num_ctus"]
