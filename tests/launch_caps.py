@@ -1,12 +1,21 @@
-"""Grid caps of the two grid-stride kernels whose workgroups reuse their LDS arrays from one
-pass to the next -- a helper, not a test.  tests/test_gpu_multipass.py sizes its batches from
-these factors so that every workgroup runs at least two passes; its CPU test reads the
-launchers' text and fails when a factor here no longer is the launcher's.
+"""Grid caps of the grid-stride kernels -- a helper, not a test.  The partition, intra and
+prediction kernels reuse their LDS arrays from one pass to the next; the copy kernel has a main
+loop and a tail loop that split the work of a pass.  tests/test_gpu_multipass.py,
+tests/test_gpu_predict_multipass.py and tests/test_gpu_copy.py size their work from these
+factors so that every workgroup runs at least two passes; the CPU test of
+tests/test_gpu_multipass.py reads the launchers' text and fails when a factor here no longer
+is the launcher's.
 
   launch_partition (vvc-mip-gpu_amd/csrc/mip_partition.hip): grid = min(groups, 8 * CUs),
       groups = frames * CTUs, one (frame, CTU) pair per pass;
   launch_intra (vvc-mip-gpu_amd/csrc/mip_intra.hip): grid = min(items, 32 * CUs),
       items = frames * CTUs * 20 -- per CTU the four 64x64 CUs, then the sixteen 32x32 blocks.
+  launch_predict (vvc-mip-gpu_amd/csrc/mip_predict.hip): grid = min(ceil(n / 16), 256 * 16)
+      workgroups of 4 waves, a wave takes 4 consecutive list items per pass (one per 16 lanes):
+      one round of the capped grid is 65 536 items, independent of the CU count;
+  launch_copy (vvc-mip-gpu_amd/csrc/mip_filter.hip): grid = min(ceil(n16 / 1024), 8 * CUs)
+      workgroups of 256 lanes, 1024 uint4 per workgroup and iteration: four per lane while
+      `i + 768 < n16`, then one per lane in the tail loop.
 """
 import os
 import re
@@ -18,6 +27,16 @@ PARTITION_GROUPS_PER_CU = 8
 INTRA_ITEMS_PER_CU = 32
 INTRA_ITEMS_PER_CTU = 20        # kItemsPerCtu = 4 + kIntraBlocks
 INTRA_BIG_ITEMS = 4             # items k < 4 of a CTU are its 64x64 CUs
+
+PREDICT_GROUPS_CAP = 256 * 16    # workgroups, whatever the device
+PREDICT_WAVES = 4               # kPredWaves
+PREDICT_ITEMS_PER_WAVE = 4      # kPredItemsPerWave
+PREDICT_ITEMS_PER_ROUND = PREDICT_GROUPS_CAP * PREDICT_WAVES * PREDICT_ITEMS_PER_WAVE   # 65 536
+PREDICT_QUADS_PER_ROUND = PREDICT_GROUPS_CAP * PREDICT_WAVES    # a wave's passes are quads q, q + 16 384, ...
+
+COPY_GROUPS_PER_CU = 8
+COPY_WORDS_PER_GROUP = 1024     # uint4 per workgroup and iteration
+COPY_MAIN_LOOP_REACH = 768      # the main loop runs while i + 768 < n16
 
 # (source file, launcher, factor): the launcher's cap reads `groups < F * cus ? groups : F * cus`
 LAUNCHERS = (
@@ -35,12 +54,24 @@ def launcher_body(source, launcher):
     return text[at:]
 
 
+def kernel_body(source, kernel):
+    """The text of `kernel` in csrc/`source`, from its name to the closing brace of its body."""
+    with open(os.path.join(CSRC, source)) as f:
+        text = f.read()
+    at = text.index("void %s(" % kernel)
+    return text[at:text.index("\n}\n", at)]
+
+
 def partition_cap(cus):
     return PARTITION_GROUPS_PER_CU * cus
 
 
 def intra_cap(cus):
     return INTRA_ITEMS_PER_CU * cus
+
+
+def copy_cap(cus):
+    return COPY_GROUPS_PER_CU * cus
 
 
 def multipass_work(cap):

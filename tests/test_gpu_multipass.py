@@ -8,6 +8,8 @@ reference (tests/partition_ref.py, tests/intra_ref.py) indexed by that order, bi
 
 The CPU test pins the cap factors to the launchers' text, so the GPU tests cannot fall back to
 single-pass coverage when a cap changes."""
+import re
+
 import numpy as np
 import pytest
 
@@ -41,6 +43,41 @@ def test_launch_caps_are_the_launchers():
         assert "constexpr int kIntraBlocks = 16;" in f.read()
     assert L.INTRA_ITEMS_PER_CTU == 4 + 16 and L.INTRA_BIG_ITEMS == 4
     assert L.passes(L.multipass_work(2048), 2048) == (2, 3) and L.passes(18, 2048) == (1, 1)
+
+
+def test_predict_and_copy_caps_are_the_launchers():
+    """The same contract for the prediction kernel (tests/test_gpu_predict_multipass.py) and the
+    copy kernel (tests/test_gpu_copy.py): their caps, the items a wave takes per pass and the reach
+    of the copy's main loop are the helper's constants, read from the launchers' and kernels' text."""
+    with open(L.CSRC + "/mip_predict.hip") as f:
+        text = f.read()
+    assert "constexpr int kPredWaves = %d;" % L.PREDICT_WAVES in text
+    assert "constexpr int kPredItemsPerWave = %d;" % L.PREDICT_ITEMS_PER_WAVE in text
+    body = L.launcher_body("mip_predict.hip", "launch_predict")
+    assert "per_group = (long long)kPredWaves * kPredItemsPerWave;" in body
+    found = re.findall(r"groups\s*=\s*std::min<long long>\(\(a\.n \+ per_group - 1\) / per_group,\s*(\d+)\s*\*\s*(\d+)\);", body)
+    assert len(found) == 1 and int(found[0][0]) * int(found[0][1]) == L.PREDICT_GROUPS_CAP == 4096, found
+    assert body.count("dim3((unsigned)groups), dim3(64 * kPredWaves)") == 2      # both instances, one grid
+    kernel = L.kernel_body("mip_predict.hip", "predict_kernel")
+    assert "q = (long long)blockIdx.x * kPredWaves + wv; q < quads; q += (long long)gridDim.x * kPredWaves" in kernel
+    assert "idx = q * kPredItemsPerWave + grp;" in kernel and "grp = lane >> 4" in kernel
+    assert L.PREDICT_ITEMS_PER_ROUND == L.PREDICT_GROUPS_CAP * L.PREDICT_WAVES * L.PREDICT_ITEMS_PER_WAVE == 65536
+    assert L.PREDICT_QUADS_PER_ROUND * L.PREDICT_ITEMS_PER_WAVE == L.PREDICT_ITEMS_PER_ROUND
+    assert L.multipass_work(L.PREDICT_ITEMS_PER_ROUND) == 152917
+    assert L.passes(152917, L.PREDICT_ITEMS_PER_ROUND) == (2, 3)
+
+    body = L.launcher_body("mip_filter.hip", "launch_copy")
+    found = re.findall(r"blocks\s*=\s*std::min<size_t>\(\(size_t\)cus \* (\d+), \(n16 \+ (\d+)\) / (\d+)\);", body)
+    assert found == [(str(L.COPY_GROUPS_PER_CU), str(L.COPY_WORDS_PER_GROUP - 1), str(L.COPY_WORDS_PER_GROUP))], found
+    assert "hipDeviceAttributeMultiprocessorCount" in body and "dim3(256)" in body
+    assert "bytes % 16 || ((uintptr_t)src | (uintptr_t)dst) % 16" in body       # the refusals of test_gpu_copy.py
+    kernel = L.kernel_body("mip_filter.hip", "copy_kernel")
+    assert "stride = (size_t)gridDim.x * %d;" % L.COPY_WORDS_PER_GROUP in kernel
+    assert "i = (size_t)blockIdx.x * %d + threadIdx.x;" % L.COPY_WORDS_PER_GROUP in kernel
+    assert "for (; i + %d < n16; i += stride)" % L.COPY_MAIN_LOOP_REACH in kernel
+    assert "for (; i < n16; i += 256)" in kernel
+    assert L.COPY_MAIN_LOOP_REACH == L.COPY_WORDS_PER_GROUP - 256
+    assert L.copy_cap(256) == 2048
 
 
 def _cus():
