@@ -406,8 +406,8 @@ int mip_partition_frames(mip_engine *e, const uint16_t *frames, const uint16_t *
  * at widths that are not multiples of 128; that is the only way the clip can fire).
  *
  * NOT modelled: VVC's [1 2 1] smoothing of Planar's reference samples for blocks of more than 32
- * samples (it needs the corner and samples beyond w and h), the angular modes, multi-reference
- * lines and ISP.
+ * samples (it needs the corner and samples beyond w and h), multi-reference lines and ISP.  The
+ * angular modes have their own entry point, mip_angular_device below.
  *
  * Cost.  SAD and SATD of `out` against the CU's originals F[(y+j)*W + x+i] (CUs right of the
  * frame wrap as in the cost tables), SATD the engine's: the 4x4 Hadamard per 4x4 block with the
@@ -443,6 +443,112 @@ int mip_intra_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_
  * cost_out / sad_out / satd_out: int32 [nframes][nCTUs*5380][2], each optional, at least one. */
 int mip_intra_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
                      int32_t *cost_out, int32_t *sad_out, int32_t *satd_out);
+
+/* Directional (angular) intra costs and their merge into the decisions (additive to ABI 7; no
+ * reference counterpart).  The angular modes 2..66 are 65 of VVC's 67 regular intra modes; VTM
+ * ranks them in the same candidate list as Planar, DC and the MIP modes by the same
+ * min(2*SAD, SATD).  mip_angular_device gives every CU the cost of each mode of a caller's list
+ * with the engine's own measure, the best of them, and merges that into the decisions.
+ *
+ * Mode codes.  MIP_MODE_ANGULAR(m) = 0x80 + m (0x82 .. 0xc2) is the best_mode value of angular
+ * mode m.  Every such code is >= 2*modes of every shape and is neither MIP_MODE_PLANAR nor
+ * MIP_MODE_DC, so mip_predict_device and mip_predict_device_ex (with or without
+ * MIP_PRED_REGULAR) skip and count such items under the existing write rule: the prediction
+ * kernel does not emit angular blocks.
+ *
+ * Definition, for the w x h CU at frame position (x, y), lw = log2 w, lh = log2 h.  R, F and
+ * the reference source rule are exactly those of mip_intra_device.
+ *
+ * Reference samples.  top[0..w) and left[0..h) are the MIP path's complete boundaries as under
+ * mip_intra_device.  The corner is one more sample: corner = R[(y-1)*W + x-1] if x > 0 and
+ * y > 0, else top[0] (that is R[(y-1)*W] in the first frame column, R[x-1] in the first frame
+ * row and 512 at (0, 0): the substitution the boundaries already make).  Above-right and
+ * below-left samples stay unavailable, with VVC's substitution as in Planar: every sample past
+ * top[w-1] equals top[w-1], every sample past left[h-1] equals left[h-1].
+ *
+ * Availability.  The corner's linear index is non-negative and below the indexes the search
+ * already reads, and no otherwise-available CU has its corner among the samples an engine filter
+ * leaves undefined, so the set is unchanged: mip_unavailable_cus(width, height, filter), or the
+ * MIP_FILTER_NONE set with caller references.
+ *
+ * Angle A(m) of mode m:
+ *     m =  2..18:   32  29  26  23  20  18  16  14  12  10   8   6   4   3   2   1   0
+ *     m = 19..34:   -1  -2  -3  -4  -6  -8 -10 -12 -14 -16 -18 -20 -23 -26 -29 -32
+ *     m = 35..50:  -29 -26 -23 -20 -18 -16 -14 -12 -10  -8  -6  -4  -3  -2  -1   0
+ *     m = 51..66:    1   2   3   4   6   8  10  12  14  16  18  20  23  26  29  32
+ * inv(A) = round(16384 / |A|) for A != 0:
+ *     |A|   1     2    3    4    6    8   10   12   14   16  18  20  23  26  29  32
+ *     inv 16384 8192 5461 4096 2731 2048 1638 1365 1170 1024 910 819 712 630 565 512
+ *
+ * Predictor.  Modes m >= 34 are the vertical class: main = top (length M = w), side = left
+ * (length S = h), (a, b) = (i, j).  Modes m < 34 are the horizontal class, the same computation
+ * transposed: main = left (M = h), side = top (S = w), (a, b) = (j, i).  The extended reference:
+ *     ref[0]  = corner
+ *     ref[k]  = main[min(k, M) - 1]                         k >= 1
+ *     ref[-k] = side'[min((k*inv + 256) >> 9, S)]           k >= 1 (reached only with A < 0),
+ *               side'[0] = corner, side'[t] = side[t-1]
+ * Sample (i, j), with d = (b+1)*A, idx = d >> 5 (arithmetic shift), f = d & 31:
+ *     P = f ? ((32 - f)*ref[a + idx + 1] + f*ref[a + idx + 2] + 16) >> 5 : ref[a + idx + 1]
+ * PDPC applies to the two pure modes only, with the weight of mip_intra_device (w(d) = 32 >> s
+ * for s = (2*d) >> scale <= 5, else 0; scale = (lw + lh - 2) >> 2):
+ *     m = 50: wL = w(i), wT = 0, refL = left[j] - corner + P
+ *     m = 18: wT = w(j), wL = 0, refT = top[i] - corner + P
+ *     P' = (refL*wL + refT*wT + (64 - wL - wT)*P + 32) >> 6
+ * For every mode out = clip(0, 1023, P or P'), in 32-bit arithmetic throughout (engine-filtered
+ * references can exceed 10 bits).
+ *
+ * NOT modelled: VVC's 4-tap cubic / Gaussian interpolation (the 2-tap filter above is VVC's
+ * chroma filter); wide-angle remapping for non-square blocks; PDPC of modes 2..17 and 51..66;
+ * reference smoothing; multi-reference lines and ISP; the real above-right / below-left samples.
+ *
+ * Cost.  Exactly mip_intra_device's: SAD and the engine's 4x4-Hadamard SATD of `out` against
+ * F[(y+j)*W + x+i] (CUs right of the frame wrap as in the cost tables), cost = min(2*SAD, SATD).
+ *
+ * modes / nmodes: a HOST list of VVC mode numbers, strictly increasing, each in 2..66, nmodes in
+ * 1..65; NULL with nmodes == 0 means all 65.  Anything else is an error before any launch.  (A
+ * caller's first pass would usually be the 33 even modes.)
+ *
+ * Tables (device pointers, each optional): d_cost, d_sad, d_satd are int32
+ * [nframes][nCTUs*5380][65], slot m - 2 for mode m.  Every entry of a given table is written:
+ * slots of modes not in the list, and all slots of unavailable CUs, are MIP_COST_UNAVAILABLE.
+ * 4-byte alignment is enough (65 is odd: there is no 8-byte demand here).
+ *
+ * Best angular mode (optional; d_ang_mode and d_ang_cost are given together), uint8 / int32
+ * [nframes][nCTUs*5380]: the lowest cost over the list, ties to the lower mode number, as the
+ * MIP_MODE_ANGULAR code and the unbiased cost; 0xff / MIP_COST_UNAVAILABLE for unavailable CUs.
+ *
+ * Merge (optional; d_best_mode and d_best_cost are given together).  On entry they hold the
+ * K = 1 decisions -- MIP, or already merged by mip_intra_device.  The decision is replaced by the
+ * best angular mode of the list only if ang_cost + bias is strictly lower; it then holds the
+ * MIP_MODE_ANGULAR code and the biased cost.  bias is in 0 .. 1<<20, else an error before any
+ * launch.  CUs whose best_cost is MIP_COST_UNAVAILABLE, and unavailable CUs, stay as they are.
+ * The merged arrays feed mip_partition_device unchanged.
+ *
+ * At least one table, the ang pair or the merge pair must be given.  Asynchronous on `stream`;
+ * reference source, the nframes <= max_batch rule with an engine filter, and the ordering on the
+ * engine's filter scratch are those of mip_intra_device.  Argument errors are reported before
+ * any launch. */
+#define MIP_ANGULAR_FIRST 2
+#define MIP_ANGULAR_LAST  66
+#define MIP_ANGULAR_MODES 65          /* table slot = m - 2 */
+#define MIP_MODE_ANGULAR(m) (0x80 + (m))   /* 0x82 .. 0xc2 */
+int mip_angular_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes,
+                       const uint8_t *modes, int nmodes,
+                       int32_t *d_cost, int32_t *d_sad, int32_t *d_satd,
+                       uint8_t *d_ang_mode, int32_t *d_ang_cost,
+                       int32_t bias, uint8_t *d_best_mode, int32_t *d_best_cost, void *stream);
+
+/* The best angular modes and, optionally, the cost table of host frames, synchronous like
+ * mip_intra_frames (it first waits for every call in flight; an open merged chunk is launched):
+ * upload, filter if the engine has one and no references are given, kernel, download, in chunks
+ * of at most max_batch frames.  cost_out: int32 [nframes][nCTUs*5380][65]; ang_mode_out /
+ * ang_cost_out (given together): [nframes][nCTUs*5380]; at least one output.  The table is
+ * 1.4 MB per CTU (about 189 MB per 1080p frame), so with cost_out the chunk is further cut so
+ * that the call's device table stays within 256 MiB (always at least one frame).  Results do not
+ * depend on the chunking. */
+int mip_angular_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
+                       const uint8_t *modes, int nmodes,
+                       int32_t *cost_out, uint8_t *ang_mode_out, int32_t *ang_cost_out);
 
 /* The whole chain on host frames, synchronous like mip_partition_frames (it first waits for every
  * call in flight; an open merged chunk is launched): in chunks of at most max_batch frames --

@@ -1,0 +1,260 @@
+// angular_plan.h -- the directional (angular) intra costs (include/mipgpu.h, mip_angular_device)
+// as per-sample and per-4x4-block arithmetic, shared by the kernel (mip_angular.hip: one lane per
+// 4x4 block, a wave-uniform loop over the mode list) and by the host restatement below
+// (angular_frames_host: the same steps, one CU at a time), plus the argmin over the list and the
+// decision merge.  Reference samples, SAD, SATD and cost are intra_plan.h's.  No HIP dependency
+// on the host side; unit-tested by tests/cpp/test_angular_plan.cpp.
+//
+// A "Ref" is intra_plan.h's: any callable ref(row, col) -> reference sample.
+#pragma once
+#include "intra_plan.h"
+
+namespace mipgpu {
+
+constexpr int kAngModes = MIP_ANGULAR_MODES;  // table slot = mode - 2
+constexpr int32_t kAngMaxBias = 1 << 20;
+
+// ---- angle and inverse angle of mode m (2..66): |A| by distance from the pure mode of the class
+MIP_INTRA_HD int ang_abs_angle(int k) {
+  constexpr int t[17] = {0, 1, 2, 3, 4, 6, 8, 10, 12, 14, 16, 18, 20, 23, 26, 29, 32};
+  return t[k];
+}
+MIP_INTRA_HD int ang_abs_inverse(int k) {  // round(16384 / |A|), 0 for A = 0
+  constexpr int t[17] = {0, 16384, 8192, 5461, 4096, 2731, 2048, 1638, 1365, 1170, 1024, 910, 819, 712, 630, 565, 512};
+  return t[k];
+}
+MIP_INTRA_HD int ang_angle(int m) {
+  const int k = m < 34 ? 18 - m : m - 50;  // horizontal class: positive towards mode 2
+  return k < 0 ? -ang_abs_angle(-k) : ang_abs_angle(k);
+}
+MIP_INTRA_HD int ang_inverse(int m) {
+  const int k = m < 34 ? 18 - m : m - 50;
+  return ang_abs_inverse(k < 0 ? -k : k);
+}
+
+// One mode of a list as the kernel takes it: mode | (A + 32) << 8 | inv << 16.
+struct AngMode {
+  int m, angle, inv;
+};
+MIP_INTRA_HD uint32_t ang_pack(int m) { return (uint32_t)m | (uint32_t)(ang_angle(m) + 32) << 8 | (uint32_t)ang_inverse(m) << 16; }
+MIP_INTRA_HD AngMode ang_unpack(uint32_t v) { return AngMode{(int)(v & 0xffu), (int)(v >> 8 & 0xffu) - 32, (int)(v >> 16)}; }
+
+// The mode list of a call: NULL with nmodes == 0 is all 65 modes, else 1..65 strictly increasing
+// mode numbers in 2..66.  packed[q] (q < n) in list order, listed: bit (m - 2) of the slots.
+struct AngList {
+  uint32_t packed[kAngModes];
+  uint32_t listed[3];
+  int n;
+};
+inline bool ang_list(const uint8_t *modes, int nmodes, AngList *out) {
+  if (!modes ? nmodes != 0 : (nmodes < 1 || nmodes > kAngModes)) return false;
+  AngList l{};
+  l.n = modes ? nmodes : kAngModes;
+  for (int q = 0, before = 0; q < l.n; q++) {
+    const int m = modes ? modes[q] : MIP_ANGULAR_FIRST + q;
+    if (m < MIP_ANGULAR_FIRST || m > MIP_ANGULAR_LAST || m <= before) return false;
+    before = m;
+    l.packed[q] = ang_pack(m);
+    l.listed[(m - 2) >> 5] |= 1u << ((m - 2) & 31);
+  }
+  *out = l;
+  return true;
+}
+MIP_INTRA_HD bool ang_listed(const uint32_t *listed, int slot) { return listed[slot >> 5] >> (slot & 31) & 1u; }
+inline bool ang_bias_ok(int32_t bias) { return bias >= 0 && bias <= kAngMaxBias; }
+
+// ---- the extended reference of the w x h CU at (x, y): top / left are the MIP path's complete
+// boundaries, the corner is R[(y-1)*W + x-1] or top[0]; samples past either end repeat the last.
+// A "Bound" gives the two boundary lines: w, h, sample(top_line, t) = top[t] or left[t], and
+// corner().  AngBound is the one over a Ref; the kernel has its own over the staged window.
+template <class Ref>
+struct AngBound {
+  const Ref &ref;
+  int x, y, w, h;
+  MIP_INTRA_HD int sample(bool top_line, int t) const { return top_line ? intra_top(ref, x, y, t) : intra_left(ref, x, y, t); }
+  MIP_INTRA_HD int corner() const { return x > 0 && y > 0 ? ref(y - 1, x - 1) : intra_top(ref, x, y, 0); }
+};
+// ref[k] of the class: VERT main = top, side = left; else the transpose.  One boundary read:
+// k <= 0 is side'[min(p, S)] with p = (-k*inv + 256) >> 9, and p == 0 (k == 0 too) is the corner.
+template <bool VERT, class Bound>
+MIP_INTRA_HD int ang_ref(const Bound &b, int k, int inv, int corner) {
+  const int M = VERT ? b.w : b.h, S = VERT ? b.h : b.w;
+  const bool main = k > 0;
+  const int p = (-k * inv + 256) >> 9;  // (used for k <= 0, reached only with A < 0)
+  const int t = main ? (k < M ? k : M) - 1 : (p < S ? p : S) - 1;
+  const int v = b.sample(main == VERT, t < 0 ? 0 : t);
+  return t < 0 ? corner : v;
+}
+// the same for A >= 0, where every k is >= 1
+template <bool VERT, class Bound>
+MIP_INTRA_HD int ang_ref_main(const Bound &b, int k) {
+  const int M = VERT ? b.w : b.h;
+  return b.sample(VERT, (k < M ? k : M) - 1);
+}
+
+MIP_INTRA_HD int ang_clip(int v) { return v < 0 ? 0 : v > 1023 ? 1023 : v; }
+
+// ---- one sample: the predictor as the contract writes it (the block step below computes the
+// same values with the per-row terms hoisted).
+template <class Bound>
+MIP_INTRA_HD int ang_sample(const Bound &b, const AngMode &md, int lw, int lh, int i, int j) {
+  const bool vert = md.m >= 34;
+  const int a = vert ? i : j, bb = vert ? j : i;
+  const int d = (bb + 1) * md.angle, idx = d >> 5, f = d & 31, c = b.corner();
+  const int r0 = vert ? ang_ref<true>(b, a + idx + 1, md.inv, c) : ang_ref<false>(b, a + idx + 1, md.inv, c);
+  int p = r0;
+  if (f) {
+    const int r1 = vert ? ang_ref<true>(b, a + idx + 2, md.inv, c) : ang_ref<false>(b, a + idx + 2, md.inv, c);
+    p = ((32 - f) * r0 + f * r1 + 16) >> 5;
+  }
+  if (md.m == 18 || md.m == 50) {
+    const int wgt = intra_pdpc_weight(a, (lw + lh - 2) >> 2);
+    const int side = b.sample(!vert, bb) - c + p;
+    p = (side * wgt + (64 - wgt) * p + 32) >> 6;
+  }
+  return ang_clip(p);
+}
+
+// ---- one 4x4 block of a CU, one mode: what one lane of the kernel computes per mode.  Along the
+// side direction (rows of the vertical class, columns of the horizontal one) idx and f are
+// constant, so the four samples of such a line need the five consecutive ref[a0+idx+1 .. +5].
+// (f == 0 needs no case of its own: ((32 - 0) * r + 16) >> 5 == r for r >= 0.)
+// org: the block's 16 original samples, row-major; (i0, j0) the block's place inside the CU.
+template <bool VERT, class Bound>
+MIP_INTRA_HD void ang_block_class(const Bound &b, const AngMode &md, int corner, int lw, int lh, int i0, int j0,
+                                  const int *org, int &sad, int &satd) {
+  const int a0 = VERT ? i0 : j0, b0 = VERT ? j0 : i0;
+  const bool pdpc = md.m == 18 || md.m == 50;
+  const int scale = (lw + lh - 2) >> 2;
+  int wgt[4] = {0, 0, 0, 0};
+  if (pdpc) {
+    MIP_INTRA_UNROLL
+    for (int c = 0; c < 4; c++) wgt[c] = intra_pdpc_weight(a0 + c, scale);
+  }
+  int d[16];
+  MIP_INTRA_UNROLL
+  for (int r = 0; r < 4; r++) {
+    const int dd = (b0 + r + 1) * md.angle, idx = dd >> 5, f = dd & 31;
+    int s[5];
+    if (md.angle >= 0) {
+      MIP_INTRA_UNROLL
+      for (int t = 0; t < 5; t++) s[t] = ang_ref_main<VERT>(b, a0 + idx + 1 + t);
+    } else {
+      MIP_INTRA_UNROLL
+      for (int t = 0; t < 5; t++) s[t] = ang_ref<VERT>(b, a0 + idx + 1 + t, md.inv, corner);
+    }
+    const int side = pdpc ? b.sample(!VERT, b0 + r) - corner : 0;
+    MIP_INTRA_UNROLL
+    for (int c = 0; c < 4; c++) {
+      int p = ((32 - f) * s[c] + f * s[c + 1] + 16) >> 5;
+      if (pdpc) p = ((side + p) * wgt[c] + (64 - wgt[c]) * p + 32) >> 6;
+      const int at = VERT ? 4 * r + c : 4 * c + r;
+      d[at] = org[at] - ang_clip(p);
+    }
+  }
+  sad = intra_sad16(d);
+  satd = intra_satd4x4(d);
+}
+template <class Bound>
+MIP_INTRA_HD void ang_block(const Bound &b, const AngMode &md, int corner, int lw, int lh, int i0, int j0, const int *org,
+                            int &sad, int &satd) {
+  if (md.m >= 34) ang_block_class<true>(b, md, corner, lw, lh, i0, j0, org, sad, satd);
+  else ang_block_class<false>(b, md, corner, lw, lh, i0, j0, org, sad, satd);
+}
+
+// ---- argmin over the list (in list order, i.e. increasing mode: ties keep the lower mode) and
+// the merge: the best angular mode replaces the current decision only if its biased cost is
+// strictly lower.  Unavailable CUs (either side) stay as they are.
+MIP_INTRA_HD void ang_best_step(uint8_t &mode, int32_t &cost, int m, int32_t c) {
+  if (c < cost) cost = c, mode = (uint8_t)MIP_MODE_ANGULAR(m);
+}
+MIP_INTRA_HD void ang_merge(uint8_t &mode, int32_t &cost, uint8_t ang_mode, int32_t ang_cost, int32_t bias) {
+  if (cost == MIP_COST_UNAVAILABLE || ang_cost == MIP_COST_UNAVAILABLE) return;
+  if (ang_cost + bias < cost) cost = ang_cost + bias, mode = ang_mode;
+}
+
+// ---- host side: one CU (every mode of the list), then the whole walk
+inline void angular_cu_host(const uint16_t *orig, const uint16_t *refs, int width, int x, int y, int lw, int lh, const AngList &list,
+                            int32_t *sad, int32_t *satd) {
+  const IntraHostRef ref{refs, width};
+  const int w = 1 << lw, h = 1 << lh;
+  const AngBound<IntraHostRef> b{ref, x, y, w, h};
+  const int corner = b.corner();
+  for (int q = 0; q < list.n; q++) sad[q] = satd[q] = 0;
+  for (int j0 = 0; j0 < h; j0 += 4)
+    for (int i0 = 0; i0 < w; i0 += 4) {
+      int org[16];
+      for (int r = 0; r < 4; r++)
+        for (int c = 0; c < 4; c++) org[4 * r + c] = orig[(size_t)(y + j0 + r) * width + x + i0 + c];
+      for (int q = 0; q < list.n; q++) {
+        int s, t;
+        ang_block(b, ang_unpack(list.packed[q]), corner, lw, lh, i0, j0, org, s, t);
+        sad[q] += s;
+        satd[q] += t;
+      }
+    }
+}
+
+// The predicted block of one CU and mode, sample by sample (ang_sample): row r at out[r * pitch].
+inline void angular_predict_cu_host(const uint16_t *refs, int width, int x, int y, int lw, int lh, int mode, uint16_t *out, int pitch) {
+  const IntraHostRef ref{refs, width};
+  const AngBound<IntraHostRef> b{ref, x, y, 1 << lw, 1 << lh};
+  const AngMode md = ang_unpack(ang_pack(mode));
+  for (int j = 0; j < (1 << lh); j++)
+    for (int i = 0; i < (1 << lw); i++) out[(size_t)j * pitch + i] = (uint16_t)ang_sample(b, md, lw, lh, i, j);
+}
+
+// Everything mip_angular_device writes, on host arrays (each output optional, the pairs given
+// together): frames / refs [nframes][height][width] (refs already resolved), unavail
+// [nctus*5380] the availability set that goes with refs, modes / nmodes the call's list; cost /
+// sad / satd [nframes][nctus*5380][65], ang_mode / ang_cost and best_mode / best_cost
+// [nframes][nctus*5380].  Returns 0, or -1 for arguments the entry point rejects (nothing
+// written).
+inline int angular_frames_host(const uint16_t *frames, const uint16_t *refs, const uint8_t *unavail, int width, int height,
+                               int nframes, const uint8_t *modes, int nmodes, int32_t *cost, int32_t *sad, int32_t *satd,
+                               uint8_t *ang_mode, int32_t *ang_cost, int32_t bias, uint8_t *best_mode, int32_t *best_cost) {
+  if (!frames || !refs || !unavail || width <= 0 || height <= 0 || width % 4 || height % 4 || nframes < 1) return -1;
+  if (!ang_mode != !ang_cost || !best_mode != !best_cost) return -1;
+  if (!cost && !sad && !satd && !ang_cost && !best_cost) return -1;
+  AngList list;
+  if (!ang_list(modes, nmodes, &list) || !ang_bias_ok(bias)) return -1;
+  const int cols = (width + 127) / 128, nctus = cols * ((height + 127) / 128);
+  const size_t fs = (size_t)width * height;
+  const int32_t none = MIP_COST_UNAVAILABLE;
+  for (int f = 0; f < nframes; f++)
+    for (int c = 0; c < nctus; c++) {
+      size_t k = (size_t)c * MIP_CUS_PER_CTU;
+      for (int s = 0; s < MIP_NUM_SHAPES; s++) {
+        const mip_shape_desc &sd = kIntraShapes[s];
+        for (int cu = 0; cu < sd.ncu; cu++, k++) {
+          int32_t a[kAngModes], b[kAngModes];
+          const bool on = !unavail[k];
+          if (on)
+            angular_cu_host(frames + f * fs, refs + f * fs, width, 128 * (c % cols) + intra_axis(sd.xb, sd.xs, sd.xd, cu % sd.ncols),
+                            128 * (c / cols) + intra_axis(sd.yb, sd.ys, sd.yd, cu / sd.ncols), intra_log2(sd.w), intra_log2(sd.h), list,
+                            a, b);
+          const size_t at = (size_t)f * nctus * MIP_CUS_PER_CTU + k;
+          for (int slot = 0; slot < kAngModes; slot++) {
+            if (cost) cost[at * kAngModes + slot] = none;
+            if (sad) sad[at * kAngModes + slot] = none;
+            if (satd) satd[at * kAngModes + slot] = none;
+          }
+          uint8_t bm = 0xff;
+          int32_t bc = none;
+          for (int q = 0; on && q < list.n; q++) {
+            const int m = ang_unpack(list.packed[q]).m;
+            const int32_t v = intra_cost(a[q], b[q]);
+            if (cost) cost[at * kAngModes + m - 2] = v;
+            if (sad) sad[at * kAngModes + m - 2] = a[q];
+            if (satd) satd[at * kAngModes + m - 2] = b[q];
+            ang_best_step(bm, bc, m, v);
+          }
+          if (ang_cost) ang_mode[at] = bm, ang_cost[at] = bc;
+          if (best_cost) ang_merge(best_mode[at], best_cost[at], bm, bc, bias);
+        }
+      }
+    }
+  return 0;
+}
+
+}  // namespace mipgpu

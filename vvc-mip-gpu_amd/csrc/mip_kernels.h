@@ -1,6 +1,6 @@
 // mip_kernels.h -- launch interface between the C-ABI host code (mipgpu.cpp, host_pipeline.cpp)
 // and the gfx950 kernels (mip_search.hip, mip_decide.hip, mip_filter.hip, mip_fixup.hip,
-// mip_predict.hip, mip_partition.hip, mip_intra.hip).  Not part of the public ABI.
+// mip_predict.hip, mip_partition.hip, mip_intra.hip, mip_angular.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -212,5 +212,27 @@ struct IntraArgs {
   int width, height, ctu_cols, nctus, nframes;
 };
 hipError_t launch_intra(const IntraArgs &a, hipStream_t s);
+
+// Angular intra costs, the best angular mode and its merge into the decisions (angular_kernel,
+// mip_angular.hip): the work items, window and lane slots of the intra kernel, a wave-uniform
+// loop over the mode list.
+struct AngularArgs {
+  const uint16_t *orig;       // as IntraArgs
+  const uint16_t *refs;
+  const uint8_t *unavail;
+  const uint32_t *slots;
+  int slots_per_block;
+  int32_t *cost, *sad, *satd; // optional tables [nframes][nctus * 5380][65], slot = mode - 2
+  uint8_t *ang_mode;          // optional, both or neither: [nframes][nctus * 5380]
+  int32_t *ang_cost;
+  uint8_t *best_mode;         // optional merge, both or neither
+  int32_t *best_cost;
+  int32_t bias;               // 0 .. 1 << 20 (checked by the caller)
+  int width, height, ctu_cols, nctus, nframes;
+  int nmodes;                 // 1..65
+  uint32_t listed[3];         // bit (mode - 2): the mode is in the list
+  uint32_t modes[65];         // the list in increasing mode order (angular_plan.h ang_pack)
+};
+hipError_t launch_angular(const AngularArgs &a, hipStream_t s);
 
 }  // namespace mipgpu

@@ -11,6 +11,7 @@
 #include <cstring>
 
 #include "mip_tables.h"
+#include "angular_plan.h"
 #include "intra_plan.h"
 #include "partition_plan.h"
 
@@ -1324,6 +1325,33 @@ static int intra_args_ok(const mip_engine *e, int nframes, bool any_output) {
   return 0;
 }
 
+// The reference source of the regular-intra kernels (mip_intra_device, mip_angular_device): the
+// caller's references, the originals, or -- as mip_predict_device -- the engine's filter applied
+// into the engine's reference scratch, ordered after that scratch's previous reader.  The caller
+// records refs_done behind its kernel when *engine_refs is set (intra_reference_done).
+static int intra_reference_source(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes, hipStream_t s,
+                                  const uint16_t **refs, bool *engine_refs) {
+  *refs = d_refs ? d_refs : d_frames;
+  *engine_refs = !d_refs && e->opts.filter != MIP_FILTER_NONE;
+  if (*engine_refs) {
+    if (nframes > e->opts.max_batch) return fail("nframes %d > max_batch %d", nframes, e->opts.max_batch);
+    if (e->refs_pending) HIP_TRY(hipStreamWaitEvent(s, e->refs_done, 0));
+    if (e->host_pending)
+      HIP_TRY(hipStreamWaitEvent(s, e->call_done[(e->host_calls - 1) % mip_engine::kCallRing], 0));
+    if (mip_filter_device(d_frames, e->d_refs, e->width, e->height, nframes, e->opts.filter, e->opts.kernel_idx, s) != 0)
+      return -1;
+    *refs = e->d_refs;
+  }
+  return 0;
+}
+static int intra_reference_done(mip_engine *e, bool engine_refs, hipStream_t s) {
+  if (engine_refs) {
+    HIP_TRY(hipEventRecord(e->refs_done, s));
+    e->refs_pending = true;
+  }
+  return 0;
+}
+
 int mip_intra_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes, int32_t *d_cost,
                      int32_t *d_sad, int32_t *d_satd, const int32_t *bias, uint8_t *d_best_mode, int32_t *d_best_cost,
                      void *stream) {
@@ -1339,17 +1367,9 @@ int mip_intra_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_
   if (flush_open(e) != 0) return -1;  // (device-API work orders itself after the host calls)
   if (ensure_intra_tables(e) != 0) return -1;
   hipStream_t s = (hipStream_t)stream;
-  const uint16_t *refs = d_refs ? d_refs : d_frames;
-  const bool engine_refs = !d_refs && e->opts.filter != MIP_FILTER_NONE;
-  if (engine_refs) {  // as mip_predict_device: filter into the engine's reference scratch
-    if (nframes > e->opts.max_batch) return fail("nframes %d > max_batch %d", nframes, e->opts.max_batch);
-    if (e->refs_pending) HIP_TRY(hipStreamWaitEvent(s, e->refs_done, 0));
-    if (e->host_pending)
-      HIP_TRY(hipStreamWaitEvent(s, e->call_done[(e->host_calls - 1) % mip_engine::kCallRing], 0));
-    if (mip_filter_device(d_frames, e->d_refs, e->width, e->height, nframes, e->opts.filter, e->opts.kernel_idx, s) != 0)
-      return -1;
-    refs = e->d_refs;
-  }
+  const uint16_t *refs = nullptr;
+  bool engine_refs = false;
+  if (intra_reference_source(e, d_frames, d_refs, nframes, s, &refs, &engine_refs) != 0) return -1;
   mipgpu::IntraArgs a{};
   a.orig = d_frames;
   a.refs = refs;
@@ -1368,11 +1388,7 @@ int mip_intra_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_
   a.nctus = e->nctus;
   a.nframes = nframes;
   HIP_TRY(mipgpu::launch_intra(a, s));
-  if (engine_refs) {
-    HIP_TRY(hipEventRecord(e->refs_done, s));
-    e->refs_pending = true;
-  }
-  return 0;
+  return intra_reference_done(e, engine_refs, s);
 }
 
 int mip_intra_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes, int32_t *cost_out,
@@ -1424,6 +1440,130 @@ int mip_intra_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs
     INTRA_TRY(hipStreamSynchronize(s));
   }
 #undef INTRA_TRY
+  e->refs_pending = false;
+  return done(0);
+}
+
+// ---------------------------------------------------------------- angular intra costs
+// The argument rules of both angular entry points (before any launch).
+static int angular_args_ok(const mip_engine *e, int nframes, const uint8_t *modes, int nmodes, bool any_output,
+                           mipgpu::AngList *list) {
+  if (intra_args_ok(e, nframes, any_output) != 0) return -1;
+  if (!mipgpu::ang_list(modes, nmodes, list))
+    return fail("angular: modes must be 1..%d strictly increasing mode numbers in %d..%d (or NULL, 0 for all)", MIP_ANGULAR_MODES,
+                MIP_ANGULAR_FIRST, MIP_ANGULAR_LAST);
+  return 0;
+}
+
+int mip_angular_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes, const uint8_t *modes,
+                       int nmodes, int32_t *d_cost, int32_t *d_sad, int32_t *d_satd, uint8_t *d_ang_mode, int32_t *d_ang_cost,
+                       int32_t bias, uint8_t *d_best_mode, int32_t *d_best_cost, void *stream) {
+  if (!e) return fail("engine is NULL");
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (!d_frames) return fail("bad angular arguments: no frames");
+  mipgpu::AngList list;
+  if (angular_args_ok(e, nframes, modes, nmodes, d_cost || d_sad || d_satd || d_ang_mode || d_ang_cost || d_best_mode || d_best_cost,
+                      &list) != 0)
+    return -1;
+  if (!d_ang_mode != !d_ang_cost) return fail("angular: d_ang_mode and d_ang_cost are given together");
+  if (!d_best_mode != !d_best_cost) return fail("angular: d_best_mode and d_best_cost are given together");
+  if (!mipgpu::ang_bias_ok(bias)) return fail("angular: the bias is outside 0..%d", (int)mipgpu::kAngMaxBias);
+  for (const void *p : {(const void *)d_cost, (const void *)d_sad, (const void *)d_satd, (const void *)d_ang_cost, (const void *)d_best_cost})
+    if (reinterpret_cast<uintptr_t>(p) & 3) return fail("angular: int32 outputs must be 4-byte aligned");
+  HIP_TRY(hipSetDevice(e->device));
+  if (flush_open(e) != 0) return -1;  // (device-API work orders itself after the host calls)
+  if (ensure_intra_tables(e) != 0) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  const uint16_t *refs = nullptr;
+  bool engine_refs = false;
+  if (intra_reference_source(e, d_frames, d_refs, nframes, s, &refs, &engine_refs) != 0) return -1;
+  mipgpu::AngularArgs a{};
+  a.orig = d_frames;
+  a.refs = refs;
+  a.unavail = e->d_pred_unavail[engine_refs ? 1 : 0];
+  a.slots = e->d_intra_slots;
+  a.slots_per_block = e->intra_slots_per_block;
+  a.cost = d_cost;
+  a.sad = d_sad;
+  a.satd = d_satd;
+  a.ang_mode = d_ang_mode;
+  a.ang_cost = d_ang_cost;
+  a.best_mode = d_best_mode;
+  a.best_cost = d_best_cost;
+  a.bias = bias;
+  a.width = e->width;
+  a.height = e->height;
+  a.ctu_cols = e->ctu_cols;
+  a.nctus = e->nctus;
+  a.nframes = nframes;
+  a.nmodes = list.n;
+  for (int k = 0; k < 3; k++) a.listed[k] = list.listed[k];
+  for (int q = 0; q < list.n; q++) a.modes[q] = list.packed[q];
+  HIP_TRY(mipgpu::launch_angular(a, s));
+  return intra_reference_done(e, engine_refs, s);
+}
+
+// With cost_out the chunk is cut so that the call's device table stays within this bound (one
+// frame at least): a 1080p frame's table is 189 MB.
+static constexpr size_t kAngularTableBytes = (size_t)256 << 20;
+
+int mip_angular_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes, const uint8_t *modes,
+                       int nmodes, int32_t *cost_out, uint8_t *ang_mode_out, int32_t *ang_cost_out) {
+  if (!e) return fail("engine is NULL");
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (!frames) return fail("bad angular arguments: no frames");
+  mipgpu::AngList list;
+  if (angular_args_ok(e, nframes, modes, nmodes, cost_out || ang_mode_out || ang_cost_out, &list) != 0) return -1;
+  if (!ang_mode_out != !ang_cost_out) return fail("angular: ang_mode_out and ang_cost_out are given together");
+  HIP_TRY(hipSetDevice(e->device));
+  if (quiesce(e) != 0) return -1;  // (host searches in flight use the engine buffers)
+  const size_t fs = (size_t)e->width * e->height, mb = (size_t)e->opts.max_batch, ncu = (size_t)e->nctus * MIP_CUS_PER_CTU;
+  const size_t entries = ncu * mipgpu::kAngModes;  // per frame of the table
+  size_t chunk = std::min(mb, (size_t)nframes);
+  if (cost_out) chunk = std::max<size_t>(1, std::min(chunk, kAngularTableBytes / (entries * sizeof(int32_t))));
+  // the call's own device buffers (through the device block cache)
+  uint16_t *t_refs = nullptr;
+  int32_t *d_cost = nullptr, *d_ang_cost = nullptr;
+  uint8_t *d_ang_mode = nullptr;
+  auto done = [&](int rc) {
+    for (void *p : {(void *)t_refs, (void *)d_cost, (void *)d_ang_cost, (void *)d_ang_mode}) dev_free(p);
+    return rc;
+  };
+#define ANG_TRY(expr)                                                                      \
+  do {                                                                                     \
+    hipError_t _e = (expr);                                                                \
+    if (_e != hipSuccess) return done(fail("%s: %s", #expr, hipGetErrorString(_e)));       \
+  } while (0)
+  uint16_t *d_refs = nullptr;
+  if (refs_or_null) {
+    d_refs = e->d_refs;
+    if (!d_refs) {
+      ANG_TRY(dev_malloc(e->device, (void **)&t_refs, chunk * fs * 2));
+      d_refs = t_refs;
+    }
+  }
+  if (cost_out) ANG_TRY(dev_malloc(e->device, (void **)&d_cost, chunk * entries * sizeof(int32_t)));
+  if (ang_cost_out) {
+    ANG_TRY(dev_malloc(e->device, (void **)&d_ang_cost, chunk * ncu * sizeof(int32_t)));
+    ANG_TRY(dev_malloc(e->device, (void **)&d_ang_mode, chunk * ncu));
+  }
+  hipStream_t s = e->stream;
+  for (size_t f0 = 0; f0 < (size_t)nframes; f0 += chunk) {
+    const size_t nb = std::min(chunk, (size_t)nframes - f0);
+    ANG_TRY(hipMemcpyAsync(e->d_frames, frames + f0 * fs, nb * fs * 2, hipMemcpyHostToDevice, s));
+    if (d_refs) ANG_TRY(hipMemcpyAsync(d_refs, refs_or_null + f0 * fs, nb * fs * 2, hipMemcpyHostToDevice, s));
+    // (without references the device entry point filters the frames itself when the engine has a filter)
+    if (mip_angular_device(e, e->d_frames, d_refs, (int)nb, modes, nmodes, d_cost, nullptr, nullptr, d_ang_mode, d_ang_cost, 0,
+                           nullptr, nullptr, s) != 0)
+      return done(-1);
+    if (cost_out) ANG_TRY(hipMemcpyAsync(cost_out + f0 * entries, d_cost, nb * entries * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (ang_cost_out) {
+      ANG_TRY(hipMemcpyAsync(ang_cost_out + f0 * ncu, d_ang_cost, nb * ncu * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      ANG_TRY(hipMemcpyAsync(ang_mode_out + f0 * ncu, d_ang_mode, nb * ncu, hipMemcpyDeviceToHost, s));
+    }
+    ANG_TRY(hipStreamSynchronize(s));
+  }
+#undef ANG_TRY
   e->refs_pending = false;
   return done(0);
 }

@@ -64,6 +64,8 @@ PART_MAX_PENALTY = 1 << 20                 # per-shape penalties of the partitio
 MODE_PLANAR = 0xF0                         # MIP_MODE_PLANAR / MIP_MODE_DC: best_mode values written by the
 MODE_DC = 0xF1                             # merge of intra_device (regular intra modes, not MIP modes)
 INTRA_MAX_BIAS = 1 << 20                   # biases of that merge: 0 .. 1<<20
+MODE_ANGULAR_BASE = 0x80                   # MIP_MODE_ANGULAR(m) = 0x80 + m: best_mode value of angular mode m (2..66)
+ANGULAR_MODES = 65                         # MIP_ANGULAR_MODES: slots of the angular tables, slot = m - 2
 PRED_REGULAR = 1                           # MIP_PRED_REGULAR: flags bit of predict(..., regular=True)
 
 
@@ -153,6 +155,8 @@ def library():
         "mip_partition_frames": (ip, [vp, vp, vp, ip, vp, vp, vp, vp, vp, vp]),
         "mip_intra_device": (ip, [vp, vp, vp, ip, vp, vp, vp, vp, vp, vp, vp]),
         "mip_intra_frames": (ip, [vp, vp, vp, ip, vp, vp, vp]),
+        "mip_angular_device": (ip, [vp, vp, vp, ip, vp, ip, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp]),
+        "mip_angular_frames": (ip, [vp, vp, vp, ip, vp, ip, vp, vp, vp]),
         "mip_time_search_device": (ctypes.c_double, [vp, vp, vp, ip, vp, ip]),
         "mip_host_stats": (ip, [vp, ctypes.POINTER(ctypes.c_uint64), ip]),
         "mip_search_census": (ip, [vp, ctypes.POINTER(ctypes.c_uint64), ip]),
@@ -563,6 +567,51 @@ class MipEngine:
                                               ctypes.c_void_p(s.cuda_stream)))
         return cost
 
+    # ------------------------------------------------- angular intra costs
+    def angular(self, frames, refs=None, modes=None, table=False) -> dict:
+        """Best angular mode of host frames (mip_angular_frames, contract in include/mipgpu.h)
+        over `modes` (strictly increasing VVC mode numbers in 2..66; None: all 65): dict of numpy
+        arrays 'ang_mode' uint8 (MODE_ANGULAR_BASE + m; 0xff for unavailable CUs) / 'ang_cost'
+        int32 [F, nCTUs*5380] and, with `table`, 'cost' int32 [F, nCTUs*5380, 65] (slot m - 2;
+        UNAVAILABLE for modes not in the list and for unavailable CUs)."""
+        f = self._frames(frames)
+        r = None if refs is None else self._frames(refs)
+        n = f.shape[0]
+        m = _modes(modes)
+        res = {"ang_mode": np.empty((n, self.cus_per_frame), np.uint8), "ang_cost": np.empty((n, self.cus_per_frame), np.int32)}
+        if table:
+            res["cost"] = np.empty((n, self.cus_per_frame, ANGULAR_MODES), np.int32)
+        with self._lock:
+            _check(library().mip_angular_frames(self._h, _ptr(f), _ptr(r), n, _ptr(m), 0 if m is None else m.size,
+                                                _ptr(res.get("cost")), _ptr(res["ang_mode"]), _ptr(res["ang_cost"])))
+        return res
+
+    def angular_device(self, frames, modes=None, cost=None, sad=None, satd=None, ang_mode=None, ang_cost=None, refs=None,
+                       bias=0, best_mode=None, best_cost=None, stream=None):
+        """Asynchronous angular intra costs and decision merge on device tensors
+        (mip_angular_device) over `modes` (a host list, see angular): `cost` / `sad` / `satd`
+        int32 [F, nCTUs*5380, 65], each optional; `ang_mode` uint8 / `ang_cost` int32
+        [F, nCTUs*5380] (given together) receive the best mode of the list and its cost;
+        `best_mode` / `best_cost` (given together) hold the K = 1 decisions of search_device, or
+        those already merged by intra_device, and are merged in place -- a CU whose best angular
+        cost plus `bias` (0 .. 1<<20) is strictly lower gets MODE_ANGULAR_BASE + m and that cost.
+        At least one output must be given."""
+        import torch
+        n = frames.shape[0]
+        m = _modes(modes)
+        want = {"cost": (cost, 4 * ANGULAR_MODES), "sad": (sad, 4 * ANGULAR_MODES), "satd": (satd, 4 * ANGULAR_MODES),
+                "ang_mode": (ang_mode, 1), "ang_cost": (ang_cost, 4), "best_mode": (best_mode, 1), "best_cost": (best_cost, 4)}
+        for name, (t, size) in want.items():
+            if t is not None and (t.numel() * t.element_size() != n * self.cus_per_frame * size or not t.is_contiguous()):
+                raise MipError(f"angular_device: {name} must be a contiguous tensor of {n * self.cus_per_frame * size} bytes")
+        if int(bias) != np.clip(int(bias), -(1 << 31), (1 << 31) - 1):
+            raise MipError("bias does not fit int32")
+        s = stream if stream is not None else torch.cuda.current_stream(frames.device)
+        with self._lock:
+            _check(library().mip_angular_device(self._h, _ptr(frames), _ptr(refs), n, _ptr(m), 0 if m is None else m.size,
+                                                _ptr(cost), _ptr(sad), _ptr(satd), _ptr(ang_mode), _ptr(ang_cost), int(bias),
+                                                _ptr(best_mode), _ptr(best_cost), ctypes.c_void_p(s.cuda_stream)))
+
     def time_search_device(self, frames, costs, refs=None, reps=10) -> float:
         with self._lock:
             ms = library().mip_time_search_device(self._h, _ptr(frames), _ptr(refs), frames.shape[0], _ptr(costs),
@@ -662,6 +711,18 @@ def _bias(bias):
     return np.ascontiguousarray(b, dtype=np.int32)
 
 
+def _modes(modes):
+    """The mode list of angular / angular_device as the uint8 host array of the C ABI (None: all
+    65 modes).  Order and range are checked by the library; an empty list is refused here, since
+    the C ABI reads it as "all"."""
+    if modes is None:
+        return None
+    m = np.asarray(modes)
+    if m.ndim != 1 or m.size == 0 or m.size > ANGULAR_MODES or np.any(m != np.clip(m, 0, 255)):
+        raise MipError("modes must be 1..%d mode numbers in 2..66" % ANGULAR_MODES)
+    return np.ascontiguousarray(m, dtype=np.uint8)
+
+
 def partition_device(best_cost, width, height, penalty=None, best_mode=None, leaf=None, ctu_cost=None, ctu_leaves=None,
                      items=None, stream=None):
     """CTU partition decision on device tensors (mip_partition_device, contract in
@@ -706,6 +767,6 @@ def filter_device(frames_in, frames_out, filter, kernel_idx=0, stream=None):
     return frames_out
 
 
-__all__ = ["MODE_PLANAR", "MODE_DC", "INTRA_MAX_BIAS", "PRED_REGULAR", "PRED_ITEM", "PRED_NONE", "pred_items", "PART_MAX_LEAVES", "PART_MAX_PENALTY", "partition_device", "MipEngine", "MipError", "build_id", "source_id", "FILTERS", "FILTER_NONE", "filter_index", "filter_device", "topk_device", "library",
+__all__ = ["MODE_PLANAR", "MODE_DC", "INTRA_MAX_BIAS", "MODE_ANGULAR_BASE", "ANGULAR_MODES", "PRED_REGULAR", "PRED_ITEM", "PRED_NONE", "pred_items", "PART_MAX_LEAVES", "PART_MAX_PENALTY", "partition_device", "MipEngine", "MipError", "build_id", "source_id", "FILTERS", "FILTER_NONE", "filter_index", "filter_device", "topk_device", "library",
            "pinned_empty", "unavailable_cus", "numa_node", "bind_thread", "device_cache", "copy_device",
            "layout", "SHAPES", "COSTS_PER_CTU", "CUS_PER_CTU", "UNAVAILABLE", "num_ctus"]
