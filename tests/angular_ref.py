@@ -63,10 +63,10 @@ def weight(d, scale):
     return np.where(s <= 5, 32 >> np.minimum(s, 5), 0)
 
 
-def predict(top, left, corner, w, h, modes=None, pdpc=True):
+def predict(top, left, corner, w, h, modes=None, pdpc=True, clip=True):
     """The predicted blocks, int64 [len(modes), n, h, w], of boundaries top [n, w], left [n, h],
     corner [n]; pdpc=False leaves the PDPC of modes 18 and 50 and the clip out (P of the
-    contract)."""
+    contract); clip=False leaves only the clip out (the value the clip of the contract sees)."""
     modes = _modes(modes)
     top, left, corner = np.asarray(top, np.int64), np.asarray(left, np.int64), np.asarray(corner, np.int64)
     lw, lh = _log2(w), _log2(h)
@@ -103,7 +103,7 @@ def predict(top, left, corner, w, h, modes=None, pdpc=True):
                 wl, wt = 0, weight(j, scale)
                 ref_l, ref_t = 0, top[:, None, :] - c + p
             p = (ref_l * wl + ref_t * wt + (64 - wl - wt) * p + 32) >> 6
-        out[q] = np.clip(p, 0, 1023) if pdpc else p
+        out[q] = np.clip(p, 0, 1023) if pdpc and clip else p
     return out
 
 

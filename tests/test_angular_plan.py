@@ -3,7 +3,9 @@ per-4x4-block arithmetic the kernel runs one lane per block, the argmin over the
 the merge -- compiled stand-alone (tests/cpp/test_angular_plan.cpp, with
 -fsanitize=address,undefined; no preloaded library) equals the numpy restatement
 tests/angular_ref.py bit for bit in every table, in the best angular mode and in the merge, on
-structured, noise and 0 / 1023 frames at 136x72 for all 65 modes; the same program checks the
+structured, noise and 0 / 1023 frames at 136x72 for all 65 modes, and on the residue sweep's
+frames and mode list (tests/edge_sweep_cases.py) at every fifth sweep size, where the exactly
+frame-sized arrays turn a read past the frame's end into a sanitizer report; the same program checks the
 argument rules (bad mode lists, a bias out of range), and lists the CUs whose corner sample an
 engine filter leaves undefined, which pins the availability set."""
 import os
@@ -15,6 +17,7 @@ import pytest
 
 import angular_cases as AC
 import angular_ref as A
+import edge_sweep_cases as E
 import mipgpu
 import size_sweep
 from mipgpu import layout
@@ -112,6 +115,44 @@ def test_host_walk_with_a_mode_list(plan_exe, tmp_path):
     assert set(np.unique(am)) <= {0x80 + m for m in modes} | {0xFF}
     mode, cost = A.merge(best_mode[:1], best_cost[:1], am, ac, 3)
     assert np.array_equal(got["best_mode"], mode) and np.array_equal(got["best_cost"], cost)
+
+
+def _walk_equals(plan_exe, tmp_path, case, w, h, bias):
+    """One frame of an edge_sweep_cases.angular_sweep_case through the stand-alone program
+    (exactly frame-sized arrays: a read past the frame's end by an available CU is an
+    AddressSanitizer report): tables, pair and merge equal the restatement."""
+    frame, refs, un, tabs = case
+    ref = {k: v[None] for k, v in tabs.items()}
+    best_mode, best_cost, dead = _decisions(ref, un, w + h)
+    got = run_plan(plan_exe, tmp_path, frame[None], refs[None], un, E.SWEEP_MODES, best_mode, best_cost, bias)
+    for key in AC.TABLES + ("ang_mode", "ang_cost"):
+        bad = np.nonzero((got[key][0] != tabs[key]).reshape(un.size, -1).any(axis=1))[0]
+        assert bad.size == 0, ((w, h), key, bad.size, bad[:4], got[key][0][bad[:4]], tabs[key][bad[:4]])
+    assert np.array_equal(got["cost"][0, :, E.SWEEP_MODES[0] - 2] == UN, un)
+    mode, cost = A.merge(best_mode, best_cost, ref["ang_mode"], ref["ang_cost"], bias)
+    assert np.array_equal(got["best_mode"], mode) and np.array_equal(got["best_cost"], cost)
+    assert np.array_equal(mode[dead], best_mode[dead])
+    return mode
+
+
+@pytest.mark.parametrize("size", E.FIFTH, ids=size_sweep.size_id)
+def test_host_walk_at_every_fifth_sweep_size(plan_exe, tmp_path, size):
+    """The residue sweep's noise frames and mode list (tests/edge_sweep_cases.py), original
+    references: partial CTUs on both axes, windows that wrap over several frame rows."""
+    w, h = size
+    mode = _walk_equals(plan_exe, tmp_path, E.angular_sweep_case(w, h), w, h, 7)
+    assert (mode >= 0x82).any() and (mode < 12).any()
+
+
+def test_host_walk_on_a_filtered_edges_frame(plan_exe, tmp_path):
+    """An `edges` frame through the oracle's separable filter at W % 128 != 0: references above
+    1023 on available CUs, that filter's availability set."""
+    w, h = 152, 176
+    assert (w, h) in E.FIFTH and w % 128
+    case = E.angular_sweep_case(w, h, "edges", E.FILTER_SEP)
+    assert E.max_boundary_or_corner(case[1], case[2], w, h) > 1023
+    assert (case[2] & ~mipgpu.unavailable_cus(w, h)).any()     # the filter takes CUs away
+    _walk_equals(plan_exe, tmp_path, case, w, h, 0)
 
 
 def test_no_available_cu_has_an_undefined_corner(plan_exe):
