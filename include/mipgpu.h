@@ -265,7 +265,9 @@ int mip_pred_layout(int width, int height, int nframes, int layout,
  * `stream`.  Reference source as in mip_search_device: d_refs NULL = the originals, or the
  * engine's filter applied into engine scratch (nframes <= max_batch then); otherwise the
  * caller's frames.  Samples of d_out that no item writes are left as they were.  d_skipped:
- * optional device word, zeroed by the caller, incremented once per item not written. */
+ * optional device word, zeroed by the caller; it holds the number of items not written when the
+ * call's work on `stream` has completed (before that its value is unspecified: the call may run
+ * more than one kernel over the list, and they settle the count between them). */
 int mip_predict_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes,
                        const mip_pred_item *d_items, int64_t n, uint16_t *d_out, int64_t out_samples,
                        uint32_t *d_skipped, void *stream);
@@ -282,7 +284,8 @@ int mip_predict_frames(mip_engine *e, const uint16_t *frames, const uint16_t *re
 
 /* Prediction with flags (additive to ABI 7).  flags == 0: exactly mip_predict_device /
  * mip_predict_frames -- outputs, skipped count and errors (those entry points are flags == 0 calls
- * of these).  Any bit other than MIP_PRED_REGULAR is an error before any launch.
+ * of these).  Any bit other than MIP_PRED_REGULAR and MIP_PRED_ANGULAR (bit 2 included) is an
+ * error before any launch.
  *
  * MIP_PRED_REGULAR: the mode condition of the write rule gains one alternative -- mode ==
  * MIP_MODE_PLANAR or mode == MIP_MODE_DC (defined with mip_intra_device below) is valid for every
@@ -293,8 +296,19 @@ int mip_predict_frames(mip_engine *e, const uint16_t *frames, const uint16_t *re
  * set are those of mip_predict_device; the originals are not read (with d_refs / refs given the
  * frames may be NULL).  So the SAD, SATD and min(2*SAD, SATD) of an emitted block against the
  * original samples are the mip_intra_device table entries of that CU and slot (0 Planar, 1 DC),
- * and the device list of mip_partition_device on merged decisions gives whole predicted frames. */
+ * and the device list of mip_partition_device on merged decisions gives whole predicted frames.
+ *
+ * MIP_PRED_ANGULAR: the mode condition gains one more alternative -- MIP_MODE_ANGULAR(2) <= mode <=
+ * MIP_MODE_ANGULAR(66) (defined with mip_angular_device below) is valid for every shape; every
+ * other condition is unchanged, and codes 0x80, 0x81, 0xc3 and above stay invalid.  Such an item's
+ * samples are exactly the `out` of the predictor under mip_angular_device for mode m = mode - 0x80,
+ * sample for sample, with the reference source and availability set of mip_predict_device; the
+ * originals are not read.  So the SAD, SATD and cost of an emitted block against the original
+ * samples are the mip_angular_device table entries of that CU and slot m - 2.  The two bits are
+ * independent: with MIP_PRED_ANGULAR alone Planar / DC items are skipped and counted.  Without the
+ * bit a call does what it did before the bit existed: same outputs, same count, same launches. */
 #define MIP_PRED_REGULAR 1u   /* flags bit: items with mode MIP_MODE_PLANAR / MIP_MODE_DC are emitted */
+#define MIP_PRED_ANGULAR 4u   /* flags bit: items with mode MIP_MODE_ANGULAR(2..66) are emitted */
 int mip_predict_device_ex(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes,
                           const mip_pred_item *d_items, int64_t n, uint16_t *d_out, int64_t out_samples,
                           uint32_t *d_skipped, unsigned flags, void *stream);
@@ -452,9 +466,10 @@ int mip_intra_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs
  *
  * Mode codes.  MIP_MODE_ANGULAR(m) = 0x80 + m (0x82 .. 0xc2) is the best_mode value of angular
  * mode m.  Every such code is >= 2*modes of every shape and is neither MIP_MODE_PLANAR nor
- * MIP_MODE_DC, so mip_predict_device and mip_predict_device_ex (with or without
- * MIP_PRED_REGULAR) skip and count such items under the existing write rule: the prediction
- * kernel does not emit angular blocks.
+ * MIP_MODE_DC, so mip_predict_device, and mip_predict_device_ex without MIP_PRED_ANGULAR, skip
+ * and count such items under the write rule; mip_predict_device_ex with MIP_PRED_ANGULAR emits
+ * their blocks -- the `out` of the predictor below -- so that the device list of
+ * mip_partition_device on decisions merged here predicts whole frames with both flag bits.
  *
  * Definition, for the w x h CU at frame position (x, y), lw = log2 w, lh = log2 h.  R, F and
  * the reference source rule are exactly those of mip_intra_device.
@@ -564,6 +579,24 @@ int mip_predicted_frames(mip_engine *e, const uint16_t *frames, const uint16_t *
                          const int32_t *penalty, const int32_t *bias,
                          uint8_t *best_mode_out, int32_t *best_cost_out, uint8_t *leaf_out,
                          int32_t *ctu_cost_out, int32_t *ctu_leaves_out, uint16_t *pred_out);
+
+/* The chain with an optional angular stage (additive to ABI 7).  flags == 0 is mip_predicted_frames
+ * exactly (that entry point is the flags == 0 call of this one; ang_modes, ang_nmodes and ang_bias
+ * are then not looked at).  Any bit other than MIP_CHAIN_ANGULAR is an error before any launch.
+ *
+ * MIP_CHAIN_ANGULAR: per chunk -- decisions-only search, the merge of mip_intra_device with `bias`,
+ * the merge of mip_angular_device over the list ang_modes / ang_nmodes with ang_bias (the merge
+ * pair only, no tables), mip_partition_device with `penalty`, prediction of the partition's own
+ * device list with MIP_PRED_REGULAR | MIP_PRED_ANGULAR.  The list and the bias follow
+ * mip_angular_device's rules (NULL with 0: all 65 modes; bias in 0 .. 1<<20); a bad list or bias is
+ * an error before any launch.  The outputs are mip_predicted_frames': best_mode_out / best_cost_out
+ * hold the decisions after both merges, pred_out every leaf's MIP, Planar, DC or angular block. */
+#define MIP_CHAIN_ANGULAR 1u   /* flags bit of mip_predicted_frames_ex: the angular stage is on */
+int mip_predicted_frames_ex(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
+                            const int32_t *penalty, const int32_t *bias,
+                            const uint8_t *ang_modes, int ang_nmodes, int32_t ang_bias, unsigned flags,
+                            uint8_t *best_mode_out, int32_t *best_cost_out, uint8_t *leaf_out,
+                            int32_t *ctu_cost_out, int32_t *ctu_leaves_out, uint16_t *pred_out);
 
 /* Streaming device-to-device copy of `bytes` (a multiple of 16, 16-byte aligned pointers),
  * asynchronous on `stream`: 16 bytes per lane, four loads in flight per lane -- the HBM copy

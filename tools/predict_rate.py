@@ -8,8 +8,13 @@ every mode of every 16x16 CU of one frame.  Those four go through mip_predict_de
 kernel instance).  Two more go through mip_predict_device_ex with MIP_PRED_REGULAR: Planar for every
 available 16x16 CU, and the item list mip_partition_device writes for the 16 frames after the
 Planar / DC merge (bias CHAIN_BIAS, penalty CHAIN_PENALTY; padding entries included, as a caller
-that makes no host round trip passes it).  HIP events per launch, warm-up first, median of
-REPS launches.  Writes the record (with mip_build_id()) to --out, default
+that makes no host round trip passes it).  With MIP_PRED_ANGULAR (the second kernel,
+mip_predict_angular.hip, behind the first): every available 16x16 CU with one angular mode of each
+class and sign in turn (modes 6, 27, 41, 60), frame layout; the list the partition writes after the
+Planar / DC merge and the merge of all 65 angular modes (bias 0), predicted with both flags; and a
+list of the same entry count that is padding only, with MIP_PRED_REGULAR alone and with both flags
+-- the difference is what the angular kernel's scan of the padding costs.  HIP events per launch,
+warm-up first, median of REPS launches.  Writes the record (with mip_build_id()) to --out, default
 profiles/predict_rate.txt."""
 import argparse
 import os
@@ -69,9 +74,9 @@ def main():
         canvas = torch.zeros(B * H * W, dtype=torch.int16, device=dev)
         scratch = torch.empty_like(canvas)
 
-        def run(name, items, out, nframes_of_case, regular=False):
-            # (regular=False passes no keyword: the four MIP cases run on older libraries too)
-            kw = {"regular": True} if regular else {}
+        def run(name, items, out, nframes_of_case, regular=False, angular=False):
+            # (a flag that is off passes no keyword: the four MIP cases run on older libraries too)
+            kw = dict({"regular": True} if regular else {}, **({"angular": True} if angular else {}))
             d_items = torch.from_numpy(items.view(np.uint8)).to(dev)
             sk = torch.zeros(1, dtype=torch.int32, device=dev)
             eng.predict_device(frames, d_items, out, skipped=sk, stream=stream, **kw)
@@ -82,6 +87,10 @@ def main():
             items = items[~padding]
             shape = layout.cu_geometry(W, H, items["cu"])
             nbytes = int((shape[3].astype(np.int64) * shape[4]).sum()) * 2
+            if nbytes == 0:                                   # (a list of padding only: nothing to copy)
+                lines.append("%-28s %9d %10.2f %9.4f %9s %10s %11.3f" % (
+                    name, d_items.numel() // mipgpu.PRED_ITEM.itemsize, 0.0, ms, "-", "-", ms / nframes_of_case / search_ms))
+                return
             nbytes16 = (nbytes + 15) // 16 * 16
             src, dst = canvas.view(torch.uint8)[:nbytes16], scratch.view(torch.uint8)[:nbytes16]
             copy_ms = median_ms(lambda: copy_device(src, dst, stream=stream), stream)
@@ -120,6 +129,24 @@ def main():
         n_regular = int(np.isin(leaves["mode"], (mipgpu.MODE_PLANAR, mipgpu.MODE_DC)).sum())
         run("frame, merged partition list", items, canvas, B, regular=True)
         lines.append("merged partition list: %d leaves (%d Planar / DC) in %d entries" % (leaves.size, n_regular, items.size))
+        # angular items (MIP_PRED_ANGULAR): one mode of each class and sign in turn
+        turn = mipgpu.MODE_ANGULAR_BASE + np.array([6, 27, 41, 60])
+        items, total = mipgpu.pred_items(W, H, frame, cu_all, turn[np.arange(cu_all.size) % 4], layout="frame", nframes=B)
+        run("frame, angular x4, 16x16", items, canvas, B, angular=True)
+        eng.angular_device(frames, bias=0, best_mode=d_best, best_cost=best_cost)
+        mipgpu.partition_device(best_cost, W, H, penalty=CHAIN_PENALTY, best_mode=d_best, items=d_list)
+        torch.cuda.synchronize()
+        items = d_list.cpu().numpy().reshape(-1).view(mipgpu.PRED_ITEM)
+        leaves = items[items["frame"] >= 0]
+        n_regular = int(np.isin(leaves["mode"], (mipgpu.MODE_PLANAR, mipgpu.MODE_DC)).sum())
+        n_angular = int(((leaves["mode"] >= mipgpu.MODE_ANGULAR_BASE + 2) & (leaves["mode"] <= mipgpu.MODE_ANGULAR_BASE + 66)).sum())
+        run("frame, angular partition list", items, canvas, B, regular=True, angular=True)
+        lines.append("angular partition list: %d leaves (%d Planar / DC, %d angular) in %d entries" % (
+            leaves.size, n_regular, n_angular, items.size))
+        padding = np.zeros(items.size, mipgpu.PRED_ITEM)
+        padding[:] = (-1, -1, -1, 0, 0)
+        run("padding only, regular", padding, canvas, B, regular=True)
+        run("padding only, both flags", padding, canvas, B, regular=True, angular=True)
     lines += ["", "x copy: prediction time / mip_copy_device of the same number of output bytes;",
               "x search/fr: prediction time per frame of the case / search time per frame."]
     text = "\n".join(lines) + "\n"

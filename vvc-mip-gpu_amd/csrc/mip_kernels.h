@@ -1,6 +1,7 @@
 // mip_kernels.h -- launch interface between the C-ABI host code (mipgpu.cpp, host_pipeline.cpp)
 // and the gfx950 kernels (mip_search.hip, mip_decide.hip, mip_filter.hip, mip_fixup.hip,
-// mip_predict.hip, mip_partition.hip, mip_intra.hip, mip_angular.hip).  Not part of the public ABI.
+// mip_predict.hip, mip_predict_angular.hip, mip_partition.hip, mip_intra.hip, mip_angular.hip).  Not
+// part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -181,6 +182,11 @@ struct PredictArgs {
                               // (launches the kernel's second instance; 0: the MIP-only one)
 };
 hipError_t launch_predict(const PredictArgs &a, hipStream_t s);
+// MIP_PRED_ANGULAR (angular_predict_kernel, mip_predict_angular.hip): the items of the same list
+// whose mode is an angular code.  Launched behind launch_predict on the same stream: it emits what
+// that kernel rejected and counted, and takes one off a.skipped for every item it emits
+// (refs_vec and regular are not used).
+hipError_t launch_predict_angular(const PredictArgs &a, hipStream_t s);
 
 // CTU partition decision (partition_kernel, mip_partition.hip): one workgroup per (frame, CTU).
 struct PartitionPenalty {

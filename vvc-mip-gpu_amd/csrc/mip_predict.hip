@@ -33,6 +33,7 @@
 #include "intra_plan.h"
 #include "mip_kernels.h"
 #include "mip_tables.h"
+#include "predict_rule.h"
 
 namespace mipgpu {
 namespace {
@@ -63,14 +64,6 @@ __device__ __forceinline__ void wave_lds_sync() {
 }
 
 __device__ __forceinline__ int ilog2i(int v) { return 31 - __clz(v); }
-
-// One list item, decoded and checked: on = it is written, reg = a regular (Planar / DC) item,
-// only ever set in the kernel's MIP_PRED_REGULAR instance.
-struct Item {
-  bool on, reg;
-  int frame, x, y, w, h, sid, modes, mode, pitch;
-  long long offset;
-};
 
 // V consecutive samples of output row yy from column xx (multiple of V): the vertical pass
 // between the anchor rows (intra.cl:871-912); anchor rows keep their values.
@@ -255,33 +248,13 @@ __device__ __forceinline__ void predict_cu(const PredictArgs &a, const Item &c, 
   wave_lds_sync();  // the next item rewrites the group's words
 }
 
-// The write rule of include/mipgpu.h, item by item.
+// The write rule of include/mipgpu.h, item by item (predict_rule.h, shared with the angular kernel).
+struct PredShapes {
+  __device__ __forceinline__ mip_shape_desc operator()(int s) const { return p_shapes[s]; }
+};
 template <bool REGULAR>
 __device__ __forceinline__ Item decode(const PredictArgs &a, const mip_pred_item &it) {
-  Item c{};
-  c.on = c.reg = false;
-  if (it.frame < 0 || it.frame >= a.nframes || it.cu < 0 || it.cu >= a.nctus * MIP_CUS_PER_CTU) return c;
-  if (a.unavail[it.cu]) return c;
-  const int ctu = it.cu / MIP_CUS_PER_CTU;
-  const uint32_t g = a.geo[it.cu - ctu * MIP_CUS_PER_CTU];  // shape | x << 8 | y << 16 inside the CTU
-  const mip_shape_desc sd = p_shapes[g & 0xffu];
-  c.w = sd.w;
-  c.h = sd.h;
-  c.sid = sd.size_id;
-  c.modes = sd.modes;
-  const bool reg = REGULAR && (it.mode == MIP_MODE_PLANAR || it.mode == MIP_MODE_DC);  // every shape has both
-  if (!reg && (it.mode < 0 || it.mode >= 2 * c.modes)) return c;
-  if (it.pitch < c.w || (it.pitch & 3) || (it.offset & 3) || it.offset < 0 || it.offset > a.out_samples) return c;
-  if (a.out_samples - it.offset < (long long)(c.h - 1) * it.pitch + c.w) return c;
-  c.frame = it.frame;
-  c.x = 128 * (ctu % a.ctu_cols) + (int)((g >> 8) & 0xffu);
-  c.y = 128 * (ctu / a.ctu_cols) + (int)((g >> 16) & 0xffu);
-  c.mode = it.mode;
-  c.pitch = it.pitch;
-  c.offset = it.offset;
-  c.reg = reg;
-  c.on = true;
-  return c;
+  return pred_decode<REGULAR, false>(a, it, PredShapes{});
 }
 
 __device__ __forceinline__ int bcast(int v, int src) { return __builtin_amdgcn_readfirstlane(__shfl(v, src, 64)); }

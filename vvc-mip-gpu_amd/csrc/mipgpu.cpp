@@ -14,6 +14,7 @@
 #include "angular_plan.h"
 #include "intra_plan.h"
 #include "partition_plan.h"
+#include "predict_rule.h"
 
 thread_local std::string g_err;
 
@@ -976,12 +977,15 @@ static int predict_launch(mip_engine *e, const uint16_t *refs, bool engine_refs,
   a.refs_vec = (reinterpret_cast<uintptr_t>(refs) & 7) == 0;
   a.regular = (flags & MIP_PRED_REGULAR) != 0;
   HIP_TRY(mipgpu::launch_predict(a, s));
+  // MIP_PRED_ANGULAR: the kernel above has rejected and counted the angular items; the angular
+  // kernel emits them behind it and takes them off the count (final in stream order)
+  if (flags & MIP_PRED_ANGULAR) HIP_TRY(mipgpu::launch_predict_angular(a, s));
   return 0;
 }
 
 static int predict_args_ok(const mip_engine *e, int nframes, const void *items, int64_t n, const void *out,
                            int64_t out_samples, unsigned flags) {
-  if (flags & ~MIP_PRED_REGULAR) return fail("unknown prediction flags 0x%x", flags);
+  if (!mipgpu::pred_flags_ok(flags)) return fail("unknown prediction flags 0x%x", flags);
   if (nframes < 1 || n < 0 || out_samples < 0 || (n && (!items || !out))) return fail("bad prediction arguments");
   if (n > kMaxCus) return fail("%lld prediction items exceed %lld per call", (long long)n, kMaxCus);
   if ((long long)nframes * e->nctus * MIP_CUS_PER_CTU > kMaxCus) return fail("%d frames exceed %lld CUs per call", nframes, kMaxCus);
@@ -1210,11 +1214,21 @@ int mip_partition_frames(mip_engine *e, const uint16_t *frames, const uint16_t *
   return done(0);
 }
 
-// The whole device chain on host frames: decisions, Planar / DC merge, partition and the
-// partition's predicted frames, chunk by chunk like mip_partition_frames.
+// The whole device chain on host frames: decisions, Planar / DC merge, (angular merge,) partition
+// and the partition's predicted frames, chunk by chunk like mip_partition_frames.
 int mip_predicted_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
                          const int32_t *penalty, const int32_t *bias, uint8_t *best_mode_out, int32_t *best_cost_out,
                          uint8_t *leaf_out, int32_t *ctu_cost_out, int32_t *ctu_leaves_out, uint16_t *pred_out) {
+  return mip_predicted_frames_ex(e, frames, refs_or_null, nframes, penalty, bias, nullptr, 0, 0, 0, best_mode_out, best_cost_out,
+                                 leaf_out, ctu_cost_out, ctu_leaves_out, pred_out);
+}
+
+// With MIP_CHAIN_ANGULAR the angular merge runs between the Planar / DC merge and the partition,
+// and the prediction emits the angular leaves too.
+int mip_predicted_frames_ex(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
+                            const int32_t *penalty, const int32_t *bias, const uint8_t *ang_modes, int ang_nmodes,
+                            int32_t ang_bias, unsigned flags, uint8_t *best_mode_out, int32_t *best_cost_out, uint8_t *leaf_out,
+                            int32_t *ctu_cost_out, int32_t *ctu_leaves_out, uint16_t *pred_out) {
   if (!e) return fail("engine is NULL");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   if (!frames) return fail("bad partition arguments: no frames");
@@ -1222,6 +1236,16 @@ int mip_predicted_frames(mip_engine *e, const uint16_t *frames, const uint16_t *
                         best_mode_out || best_cost_out || leaf_out || ctu_cost_out || ctu_leaves_out || pred_out) != 0)
     return -1;
   if (!mipgpu::intra_bias_ok(bias)) return fail("intra: a bias is outside 0..%d", (int)mipgpu::kIntraMaxBias);
+  mipgpu::AngList ang_list_checked;  // (mip_angular_device checks the caller's list again, chunk by chunk)
+  switch (mipgpu::predicted_ex_args(flags, ang_modes, ang_nmodes, ang_bias, &ang_list_checked)) {
+    case mipgpu::kPredictedExOk: break;
+    case mipgpu::kPredictedExFlags: return fail("unknown chain flags 0x%x", flags);
+    case mipgpu::kPredictedExModes:
+      return fail("angular: modes must be 1..%d strictly increasing mode numbers in %d..%d (or NULL, 0 for all)", MIP_ANGULAR_MODES,
+                  MIP_ANGULAR_FIRST, MIP_ANGULAR_LAST);
+    case mipgpu::kPredictedExBias: return fail("angular: the bias is outside 0..%d", (int)mipgpu::kAngMaxBias);
+  }
+  const bool angular = (flags & MIP_CHAIN_ANGULAR) != 0;
   if (e->opts.best_k != 1) return fail("mip_predicted_frames needs best_k <= 1 (got %d)", e->opts.best_k);
   HIP_TRY(hipSetDevice(e->device));
   if (quiesce(e) != 0) return -1;  // (host searches in flight use the engine buffers)
@@ -1270,6 +1294,9 @@ int mip_predicted_frames(mip_engine *e, const uint16_t *frames, const uint16_t *
       return done(-1);
     if (mip_intra_device(e, e->d_frames, d_refs, (int)nb, nullptr, nullptr, nullptr, bias, e->d_best, e->d_best_cost, s) != 0)
       return done(-1);
+    if (angular && mip_angular_device(e, e->d_frames, d_refs, (int)nb, ang_modes, ang_nmodes, nullptr, nullptr, nullptr, nullptr,
+                                      nullptr, ang_bias, e->d_best, e->d_best_cost, s) != 0)
+      return done(-1);
     // the list's frame indexes and offsets are the chunk's own: 0 .. nb-1 into d_pred
     if (mip_partition_device(e->d_best_cost, e->d_best, e->width, e->height, (int)nb, penalty, e->d_part_leaf, d_ctu_cost,
                              d_ctu_leaves, d_items, s) != 0)
@@ -1278,7 +1305,7 @@ int mip_predicted_frames(mip_engine *e, const uint16_t *frames, const uint16_t *
       CHAIN_TRY(hipMemsetAsync(d_pred, 0xff, nb * fs * 2, s));  // MIP_PRED_NONE
       const uint16_t *refs = d_refs ? d_refs : engine_refs ? e->d_refs : e->d_frames;
       if (predict_launch(e, refs, engine_refs, (int)nb, d_items, (int64_t)(nb * per_frame), d_pred, (int64_t)(nb * fs), nullptr,
-                         MIP_PRED_REGULAR, s) != 0)
+                         angular ? MIP_PRED_REGULAR | MIP_PRED_ANGULAR : MIP_PRED_REGULAR, s) != 0)
         return done(-1);
       CHAIN_TRY(hipMemcpyAsync(pred_out + f0 * fs, d_pred, nb * fs * 2, hipMemcpyDeviceToHost, s));
     }

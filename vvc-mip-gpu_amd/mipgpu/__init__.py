@@ -67,6 +67,8 @@ INTRA_MAX_BIAS = 1 << 20                   # biases of that merge: 0 .. 1<<20
 MODE_ANGULAR_BASE = 0x80                   # MIP_MODE_ANGULAR(m) = 0x80 + m: best_mode value of angular mode m (2..66)
 ANGULAR_MODES = 65                         # MIP_ANGULAR_MODES: slots of the angular tables, slot = m - 2
 PRED_REGULAR = 1                           # MIP_PRED_REGULAR: flags bit of predict(..., regular=True)
+PRED_ANGULAR = 4                           # MIP_PRED_ANGULAR: flags bit of predict(..., angular=True)
+CHAIN_ANGULAR = 1                          # MIP_CHAIN_ANGULAR: flags bit of mip_predicted_frames_ex (the angular stage)
 
 
 class _Opts(ctypes.Structure):
@@ -151,6 +153,7 @@ def library():
         "mip_predict_device_ex": (ip, [vp, vp, vp, ip, vp, i64, vp, i64, vp, ctypes.c_uint, vp]),
         "mip_predict_frames_ex": (ip, [vp, vp, vp, ip, vp, i64, vp, i64, ctypes.c_uint, ctypes.POINTER(i64)]),
         "mip_predicted_frames": (ip, [vp, vp, vp, ip, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "mip_predicted_frames_ex": (ip, [vp, vp, vp, ip, vp, vp, vp, ip, ctypes.c_int32, ctypes.c_uint, vp, vp, vp, vp, vp, vp]),
         "mip_partition_device": (ip, [vp, vp, ip, ip, ip, vp, vp, vp, vp, vp, vp]),
         "mip_partition_frames": (ip, [vp, vp, vp, ip, vp, vp, vp, vp, vp, vp]),
         "mip_intra_device": (ip, [vp, vp, vp, ip, vp, vp, vp, vp, vp, vp, vp]),
@@ -442,45 +445,50 @@ class MipEngine:
             _check(library().mip_check_input(self._h, ctypes.c_void_p(s.cuda_stream)))
 
     # ------------------------------------------------------- prediction output
-    def predict(self, frames, items, out_samples, refs=None, regular=False):
+    def predict(self, frames, items, out_samples, refs=None, regular=False, angular=False):
         """Predicted samples of the list `items` (PRED_ITEM array, see pred_items) for host
         frames (mip_predict_frames).  Returns (uint16 array of out_samples, skipped): samples
         no item wrote are PRED_NONE; skipped counts the items that were not written
         (unavailable CUs, mode "none", blocks that do not fit).  regular=True
         (mip_predict_frames_ex, MIP_PRED_REGULAR): items with mode MODE_PLANAR / MODE_DC are
-        emitted too -- the Planar / DC blocks whose costs intra() reports."""
+        emitted too -- the Planar / DC blocks whose costs intra() reports.  angular=True
+        (MIP_PRED_ANGULAR): items with mode MODE_ANGULAR_BASE + m, m in 2..66, are emitted too --
+        the blocks whose costs angular() reports."""
+        flags = (PRED_REGULAR if regular else 0) | (PRED_ANGULAR if angular else 0)
         f = self._frames(frames)
         r = None if refs is None else self._frames(refs)
         it = np.ascontiguousarray(items, dtype=PRED_ITEM)
         out = np.empty(int(out_samples), np.uint16)
         skipped = ctypes.c_int64()
         with self._lock:
-            if regular:
+            if flags:
                 _check(library().mip_predict_frames_ex(self._h, _ptr(f), _ptr(r), f.shape[0], _ptr(it), it.size, _ptr(out),
-                                                       int(out_samples), PRED_REGULAR, ctypes.byref(skipped)))
+                                                       int(out_samples), flags, ctypes.byref(skipped)))
             else:
                 _check(library().mip_predict_frames(self._h, _ptr(f), _ptr(r), f.shape[0], _ptr(it), it.size, _ptr(out),
                                                     int(out_samples), ctypes.byref(skipped)))
         return out, int(skipped.value)
 
-    def predict_device(self, frames, items, out, refs=None, skipped=None, stream=None, regular=False):
+    def predict_device(self, frames, items, out, refs=None, skipped=None, stream=None, regular=False, angular=False):
         """Asynchronous prediction on device tensors (mip_predict_device): `items` is a uint8
         tensor of the PRED_ITEM bytes (torch.from_numpy(items.view(np.uint8)).cuda()), `out` a
         uint16 / int16 tensor the blocks are written into (other samples are left as they are),
         `skipped` an optional zeroed int32 tensor of one element that counts the items not
-        written.  regular=True (mip_predict_device_ex, MIP_PRED_REGULAR): items with mode
+        written (final when the call's work on the stream has completed).  regular=True (mip_predict_device_ex, MIP_PRED_REGULAR): items with mode
         MODE_PLANAR / MODE_DC are emitted too, so the item list of partition_device on merged
-        decisions gives whole predicted frames.  Returns `out`."""
+        decisions gives whole predicted frames.  angular=True (MIP_PRED_ANGULAR): items with an
+        angular mode code are emitted too, by a second kernel behind the first.  Returns `out`."""
         import torch
+        flags = (PRED_REGULAR if regular else 0) | (PRED_ANGULAR if angular else 0)
         nbytes = items.numel() * items.element_size()
         if nbytes % PRED_ITEM.itemsize:
             raise MipError("predict_device: items is not a whole number of %d-byte entries" % PRED_ITEM.itemsize)
         s = stream if stream is not None else torch.cuda.current_stream(frames.device)
         with self._lock:
-            if regular:
+            if flags:
                 _check(library().mip_predict_device_ex(self._h, _ptr(frames), _ptr(refs), frames.shape[0], _ptr(items),
                                                        nbytes // PRED_ITEM.itemsize, _ptr(out), out.numel(), _ptr(skipped),
-                                                       PRED_REGULAR, ctypes.c_void_p(s.cuda_stream)))
+                                                       flags, ctypes.c_void_p(s.cuda_stream)))
             else:
                 _check(library().mip_predict_device(self._h, _ptr(frames), _ptr(refs), frames.shape[0], _ptr(items),
                                                     nbytes // PRED_ITEM.itemsize, _ptr(out), out.numel(), _ptr(skipped),
@@ -494,10 +502,25 @@ class MipEngine:
         uint8 / 'best_cost' int32 (the merged decisions) / 'leaf' uint8 [F, nCTUs*5380], 'ctu_cost'
         / 'ctu_leaves' int32 [F, nCTUs] and 'pred' uint16 [F, H, W] -- every leaf's MIP, Planar or
         DC block at its place, PRED_NONE where no leaf is (CTUs without a partition)."""
+        return self.predicted_frames_ex(frames, penalty=penalty, bias=bias, refs=refs)
+
+    def predicted_frames_ex(self, frames, penalty=None, bias=None, refs=None, angular=None, angular_bias=0) -> dict:
+        """predicted_frames with an optional angular stage (mip_predicted_frames_ex).  angular=None:
+        exactly predicted_frames (mip_predicted_frames is called).  angular="all" or a list of
+        strictly increasing VVC mode numbers in 2..66: the merge of angular_device over that list
+        with `angular_bias` (0 .. 1<<20) runs between the Planar / DC merge and the partition, and
+        the prediction emits the angular leaves too -- 'best_mode' / 'best_cost' are the decisions
+        after both merges, 'pred' holds every leaf's MIP, Planar, DC or angular block."""
         f = self._frames(frames)
         r = None if refs is None else self._frames(refs)
         n = f.shape[0]
         pen, b = _penalty(penalty), _bias(bias)
+        if angular is not None:
+            if isinstance(angular, str) and angular != "all":
+                raise MipError('angular must be None, "all" or a list of modes')
+            m = None if isinstance(angular, str) else _modes(angular)
+            if int(angular_bias) != np.clip(int(angular_bias), -(1 << 31), (1 << 31) - 1):
+                raise MipError("bias does not fit int32")
         res = {"best_mode": np.empty((n, self.cus_per_frame), np.uint8),
                "best_cost": np.empty((n, self.cus_per_frame), np.int32),
                "leaf": np.empty((n, self.cus_per_frame), np.uint8),
@@ -505,9 +528,15 @@ class MipEngine:
                "ctu_leaves": np.empty((n, self.nctus), np.int32),
                "pred": np.empty((n, self.height, self.width), np.uint16)}
         with self._lock:
-            _check(library().mip_predicted_frames(self._h, _ptr(f), _ptr(r), n, _ptr(pen), _ptr(b), _ptr(res["best_mode"]),
-                                                  _ptr(res["best_cost"]), _ptr(res["leaf"]), _ptr(res["ctu_cost"]),
-                                                  _ptr(res["ctu_leaves"]), _ptr(res["pred"])))
+            if angular is None:
+                _check(library().mip_predicted_frames(self._h, _ptr(f), _ptr(r), n, _ptr(pen), _ptr(b), _ptr(res["best_mode"]),
+                                                      _ptr(res["best_cost"]), _ptr(res["leaf"]), _ptr(res["ctu_cost"]),
+                                                      _ptr(res["ctu_leaves"]), _ptr(res["pred"])))
+            else:
+                _check(library().mip_predicted_frames_ex(self._h, _ptr(f), _ptr(r), n, _ptr(pen), _ptr(b), _ptr(m),
+                                                         0 if m is None else m.size, int(angular_bias), CHAIN_ANGULAR,
+                                                         _ptr(res["best_mode"]), _ptr(res["best_cost"]), _ptr(res["leaf"]),
+                                                         _ptr(res["ctu_cost"]), _ptr(res["ctu_leaves"]), _ptr(res["pred"])))
         return res
 
     # ------------------------------------------------------- partition decision
@@ -767,6 +796,6 @@ def filter_device(frames_in, frames_out, filter, kernel_idx=0, stream=None):
     return frames_out
 
 
-__all__ = ["MODE_PLANAR", "MODE_DC", "INTRA_MAX_BIAS", "MODE_ANGULAR_BASE", "ANGULAR_MODES", "PRED_REGULAR", "PRED_ITEM", "PRED_NONE", "pred_items", "PART_MAX_LEAVES", "PART_MAX_PENALTY", "partition_device", "MipEngine", "MipError", "build_id", "source_id", "FILTERS", "FILTER_NONE", "filter_index", "filter_device", "topk_device", "library",
+__all__ = ["MODE_PLANAR", "MODE_DC", "INTRA_MAX_BIAS", "MODE_ANGULAR_BASE", "ANGULAR_MODES", "PRED_REGULAR", "PRED_ANGULAR", "CHAIN_ANGULAR", "PRED_ITEM", "PRED_NONE", "pred_items", "PART_MAX_LEAVES", "PART_MAX_PENALTY", "partition_device", "MipEngine", "MipError", "build_id", "source_id", "FILTERS", "FILTER_NONE", "filter_index", "filter_device", "topk_device", "library",
            "pinned_empty", "unavailable_cus", "numa_node", "bind_thread", "device_cache", "copy_device",
            "layout", "SHAPES", "COSTS_PER_CTU", "CUS_PER_CTU", "UNAVAILABLE", "num_ctus"]
