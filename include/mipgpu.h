@@ -565,6 +565,45 @@ int mip_angular_frames(mip_engine *e, const uint16_t *frames, const uint16_t *re
                        const uint8_t *modes, int nmodes,
                        int32_t *cost_out, uint8_t *ang_mode_out, int32_t *ang_cost_out);
 
+/* Coarse-to-fine angular mode search in one launch (additive to ABI 7; no reference counterpart):
+ * every CU ranks the caller's list, then also evaluates the +-1 neighbours of its own best few
+ * modes -- the second pass of an encoder's mode search, per CU, on the windows the first pass
+ * staged.  Everything not said here is mip_angular_device's, word for word: reference source,
+ * corner, availability set, predictor, cost, list rules, bias range, table layout, merge rule, the
+ * "at least one output" rule (d_ang_tried counts as an output), asynchrony, and argument errors
+ * reported before any launch.
+ *
+ * seeds is in 1 .. MIP_ANGULAR_MAX_SEEDS, anything else is an error before any launch.  For every
+ * available CU, with L the caller's list:
+ *   Seeds.       The min(seeds, nmodes) modes of L with the lowest cost, ties to the lower mode
+ *                number: the first entries of L sorted by (cost, mode).
+ *   Candidates.  C = { s - 1, s + 1 : s a seed } within [2, 66] and not in L, as a set: no wrap
+ *                between 2 and 66, a neighbour reached from two seeds counts once.
+ *   Evaluated.   E = L u C.  The ang pair is the minimum of (cost, mode) over E, as the
+ *                MIP_MODE_ANGULAR code and the unbiased cost; the merge uses that pair exactly as
+ *                mip_angular_device merges its own.
+ *   Tables.      For this CU the slots of E hold their values, every other slot
+ *                MIP_COST_UNAVAILABLE.  Unavailable CUs are MIP_COST_UNAVAILABLE in every slot.
+ *   d_ang_tried  (optional) uint8 [nframes][nCTUs*5380]: |E|, and 0 for unavailable CUs -- how
+ *                many modes were evaluated per CU, without downloading a table.
+ * Consequences: with all 65 modes listed C is empty and every output equals mip_angular_device's
+ * (d_ang_tried is 65); the refined cost is never above the list's best and never below the
+ * 65-mode best. */
+#define MIP_ANGULAR_MAX_SEEDS 3
+int mip_angular_refine_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes,
+                              const uint8_t *modes, int nmodes, int seeds,
+                              int32_t *d_cost, int32_t *d_sad, int32_t *d_satd,
+                              uint8_t *d_ang_mode, int32_t *d_ang_cost, uint8_t *d_ang_tried,
+                              int32_t bias, uint8_t *d_best_mode, int32_t *d_best_cost, void *stream);
+
+/* mip_angular_refine_device on host frames, synchronous and chunked like mip_angular_frames (the
+ * same 256 MiB cut of the device table with cost_out).  tried_out: uint8 [nframes][nCTUs*5380],
+ * optional; ang_mode_out / ang_cost_out given together; at least one output.  Results do not
+ * depend on the chunking. */
+int mip_angular_refine_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
+                              const uint8_t *modes, int nmodes, int seeds,
+                              int32_t *cost_out, uint8_t *ang_mode_out, int32_t *ang_cost_out, uint8_t *tried_out);
+
 /* The whole chain on host frames, synchronous like mip_partition_frames (it first waits for every
  * call in flight; an open merged chunk is launched): in chunks of at most max_batch frames --
  * upload, filter if the engine has one and no references are given, decisions-only search, the

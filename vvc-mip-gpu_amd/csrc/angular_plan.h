@@ -4,6 +4,9 @@
 // (angular_frames_host: the same steps, one CU at a time), plus the argmin over the list and the
 // decision merge.  Reference samples, SAD, SATD and cost are intra_plan.h's.  No HIP dependency
 // on the host side; unit-tested by tests/cpp/test_angular_plan.cpp.
+// The coarse-to-fine search (mip_angular_refine_device, mip_angular_refine.hip) adds the running
+// top three of the list, the seed and candidate step, and its own host walk
+// (angular_refine_frames_host); unit-tested by tests/cpp/test_angular_refine.cpp.
 //
 // A "Ref" is intra_plan.h's: any callable ref(row, col) -> reference sample.
 #pragma once
@@ -173,6 +176,76 @@ MIP_INTRA_HD void ang_merge(uint8_t &mode, int32_t &cost, uint8_t ang_mode, int3
   if (ang_cost + bias < cost) cost = ang_cost + bias, mode = ang_mode;
 }
 
+// ---- coarse-to-fine (mip_angular_refine_device): the running top three of the list, the
+// candidate step and the argmin over modes that arrive in any order.
+constexpr int kAngMaxSeeds = MIP_ANGULAR_MAX_SEEDS;
+inline bool ang_seeds_ok(int seeds) { return seeds >= 1 && seeds <= kAngMaxSeeds; }
+
+// The three lowest (cost, mode) of the modes seen so far, lowest first; mode 0 = no entry.  The
+// list arrives in increasing mode order and only a strictly lower cost moves an entry down, so
+// ties keep the lower mode in front.
+struct AngTop {
+  int32_t c0, c1, c2;
+  int m0, m1, m2;
+};
+MIP_INTRA_HD AngTop ang_top_none() { return AngTop{MIP_COST_UNAVAILABLE, MIP_COST_UNAVAILABLE, MIP_COST_UNAVAILABLE, 0, 0, 0}; }
+MIP_INTRA_HD void ang_top_step(AngTop &t, int m, int32_t c) {
+  const bool b0 = c < t.c0, b1 = c < t.c1, b2 = c < t.c2;
+  t.c2 = b1 ? t.c1 : b2 ? c : t.c2;
+  t.m2 = b1 ? t.m1 : b2 ? m : t.m2;
+  t.c1 = b0 ? t.c0 : b1 ? c : t.c1;
+  t.m1 = b0 ? t.m0 : b1 ? m : t.m1;
+  t.c0 = b0 ? c : t.c0;
+  t.m0 = b0 ? m : t.m0;
+}
+
+// A set of modes as the listed-slot mask: bit (m - 2).
+struct AngSet {
+  uint32_t w0, w1, w2;
+};
+MIP_INTRA_HD void ang_set_add(AngSet &s, int m, bool on) {  // m in 2..66 where `on`
+  const int slot = m - MIP_ANGULAR_FIRST;
+  const uint32_t bit = on ? 1u << (slot & 31) : 0u;
+  s.w0 |= (slot >> 5) == 0 ? bit : 0u;
+  s.w1 |= (slot >> 5) == 1 ? bit : 0u;
+  s.w2 |= (slot >> 5) == 2 ? bit : 0u;
+}
+MIP_INTRA_HD int ang_set_count(const AngSet &s) { return __builtin_popcount(s.w0) + __builtin_popcount(s.w1) + __builtin_popcount(s.w2); }
+// Takes the lowest mode out of the set and returns it; 0 if the set is empty.
+MIP_INTRA_HD int ang_set_pop(AngSet &s) {
+  const int w = s.w0 ? 0 : s.w1 ? 1 : 2;
+  const uint32_t v = s.w0 ? s.w0 : s.w1 ? s.w1 : s.w2;
+  const int bit = v ? __builtin_ctz(v) : 0;
+  const uint32_t rest = v & (v - 1u);
+  s.w0 = w == 0 ? rest : s.w0;
+  s.w1 = w == 1 ? rest : s.w1;
+  s.w2 = w == 2 ? rest : s.w2;
+  return v ? MIP_ANGULAR_FIRST + 32 * w + bit : 0;
+}
+// The seed and candidate step: the first min(nseeds, entries) entries of the CU's top list are
+// its seeds; the candidates are their +-1 neighbours inside 2..66 (no wrap) that the list does
+// not hold, as a set -- a neighbour of two seeds counts once -- which ang_set_pop hands out in
+// increasing mode order.
+MIP_INTRA_HD AngSet ang_candidates(const AngTop &t, int nseeds, const uint32_t *listed) {
+  AngSet s{0u, 0u, 0u};
+  const int seed[kAngMaxSeeds] = {t.m0, t.m1, t.m2};
+  MIP_INTRA_UNROLL
+  for (int q = 0; q < kAngMaxSeeds; q++) {
+    const bool is = q < nseeds && seed[q] != 0;
+    ang_set_add(s, seed[q] - 1, is && seed[q] > MIP_ANGULAR_FIRST);
+    ang_set_add(s, seed[q] + 1, is && seed[q] < MIP_ANGULAR_LAST);
+  }
+  s.w0 &= ~listed[0];
+  s.w1 &= ~listed[1];
+  s.w2 &= ~listed[2];
+  return s;
+}
+// argmin of (cost, mode) over modes in any order
+MIP_INTRA_HD void ang_best_step_any(uint8_t &mode, int32_t &cost, int m, int32_t c) {
+  const uint8_t code = (uint8_t)MIP_MODE_ANGULAR(m);
+  if (c < cost || (c == cost && code < mode)) cost = c, mode = code;
+}
+
 // ---- host side: one CU (every mode of the list), then the whole walk
 inline void angular_cu_host(const uint16_t *orig, const uint16_t *refs, int width, int x, int y, int lw, int lh, const AngList &list,
                             int32_t *sad, int32_t *satd) {
@@ -250,6 +323,70 @@ inline int angular_frames_host(const uint16_t *frames, const uint16_t *refs, con
             ang_best_step(bm, bc, m, v);
           }
           if (ang_cost) ang_mode[at] = bm, ang_cost[at] = bc;
+          if (best_cost) ang_merge(best_mode[at], best_cost[at], bm, bc, bias);
+        }
+      }
+    }
+  return 0;
+}
+
+// Everything mip_angular_refine_device writes, on host arrays: angular_frames_host's arguments
+// plus seeds and the optional tried [nframes][nctus*5380].  Per available CU the list's costs, the
+// running top three, the candidate step, the candidates' costs, then the pair over both.
+inline int angular_refine_frames_host(const uint16_t *frames, const uint16_t *refs, const uint8_t *unavail, int width, int height,
+                                      int nframes, const uint8_t *modes, int nmodes, int seeds, int32_t *cost, int32_t *sad,
+                                      int32_t *satd, uint8_t *ang_mode, int32_t *ang_cost, uint8_t *tried, int32_t bias,
+                                      uint8_t *best_mode, int32_t *best_cost) {
+  if (!frames || !refs || !unavail || width <= 0 || height <= 0 || width % 4 || height % 4 || nframes < 1) return -1;
+  if (!ang_mode != !ang_cost || !best_mode != !best_cost) return -1;
+  if (!cost && !sad && !satd && !ang_cost && !best_cost && !tried) return -1;
+  AngList list;
+  if (!ang_list(modes, nmodes, &list) || !ang_bias_ok(bias) || !ang_seeds_ok(seeds)) return -1;
+  const int nseeds = seeds < list.n ? seeds : list.n;
+  const int cols = (width + 127) / 128, nctus = cols * ((height + 127) / 128);
+  const size_t fs = (size_t)width * height;
+  const int32_t none = MIP_COST_UNAVAILABLE;
+  for (int f = 0; f < nframes; f++)
+    for (int c = 0; c < nctus; c++) {
+      size_t k = (size_t)c * MIP_CUS_PER_CTU;
+      for (int s = 0; s < MIP_NUM_SHAPES; s++) {
+        const mip_shape_desc &sd = kIntraShapes[s];
+        for (int cu = 0; cu < sd.ncu; cu++, k++) {
+          const size_t at = (size_t)f * nctus * MIP_CUS_PER_CTU + k;
+          for (int slot = 0; slot < kAngModes; slot++) {
+            if (cost) cost[at * kAngModes + slot] = none;
+            if (sad) sad[at * kAngModes + slot] = none;
+            if (satd) satd[at * kAngModes + slot] = none;
+          }
+          uint8_t bm = 0xff;
+          int32_t bc = none;
+          int evaluated = 0;
+          if (!unavail[k]) {
+            const int x = 128 * (c % cols) + intra_axis(sd.xb, sd.xs, sd.xd, cu % sd.ncols);
+            const int y = 128 * (c / cols) + intra_axis(sd.yb, sd.ys, sd.yd, cu / sd.ncols);
+            const int lw = intra_log2(sd.w), lh = intra_log2(sd.h);
+            int32_t a[kAngModes], b[kAngModes];
+            auto take = [&](const AngList &l) {
+              angular_cu_host(frames + f * fs, refs + f * fs, width, x, y, lw, lh, l, a, b);
+              for (int q = 0; q < l.n; q++) {
+                const int m = ang_unpack(l.packed[q]).m;
+                if (cost) cost[at * kAngModes + m - 2] = intra_cost(a[q], b[q]);
+                if (sad) sad[at * kAngModes + m - 2] = a[q];
+                if (satd) satd[at * kAngModes + m - 2] = b[q];
+                ang_best_step_any(bm, bc, m, intra_cost(a[q], b[q]));
+              }
+              evaluated += l.n;
+            };
+            take(list);
+            AngTop top = ang_top_none();
+            for (int q = 0; q < list.n; q++) ang_top_step(top, ang_unpack(list.packed[q]).m, intra_cost(a[q], b[q]));
+            AngSet cand = ang_candidates(top, nseeds, list.listed);
+            AngList fine{};
+            for (int m = ang_set_pop(cand); m; m = ang_set_pop(cand)) fine.packed[fine.n++] = ang_pack(m);
+            if (fine.n) take(fine);
+          }
+          if (ang_cost) ang_mode[at] = bm, ang_cost[at] = bc;
+          if (tried) tried[at] = (uint8_t)evaluated;
           if (best_cost) ang_merge(best_mode[at], best_cost[at], bm, bc, bias);
         }
       }

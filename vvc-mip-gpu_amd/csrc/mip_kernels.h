@@ -1,7 +1,7 @@
 // mip_kernels.h -- launch interface between the C-ABI host code (mipgpu.cpp, host_pipeline.cpp)
 // and the gfx950 kernels (mip_search.hip, mip_decide.hip, mip_filter.hip, mip_fixup.hip,
-// mip_predict.hip, mip_predict_angular.hip, mip_partition.hip, mip_intra.hip, mip_angular.hip).  Not
-// part of the public ABI.
+// mip_predict.hip, mip_predict_angular.hip, mip_partition.hip, mip_intra.hip, mip_angular.hip,
+// mip_angular_refine.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -240,5 +240,14 @@ struct AngularArgs {
   uint32_t modes[65];         // the list in increasing mode order (angular_plan.h ang_pack)
 };
 hipError_t launch_angular(const AngularArgs &a, hipStream_t s);
+
+// Coarse-to-fine angular search (angular_refine_kernel, mip_angular_refine.hip): angular_kernel's
+// items, window and coarse loop, then per CU the +-1 neighbours of its own best `nseeds` modes.
+struct AngularRefineArgs : AngularArgs {
+  uint8_t *tried;             // optional: [nframes][nctus * 5380] modes evaluated per CU
+  int nseeds;                 // min(seeds, nmodes): 1..3
+  uint32_t all[65];           // ang_pack of every mode 2..66 (staged in LDS: a per-lane lookup)
+};
+hipError_t launch_angular_refine(const AngularRefineArgs &a, hipStream_t s);
 
 }  // namespace mipgpu

@@ -1482,16 +1482,21 @@ static int angular_args_ok(const mip_engine *e, int nframes, const uint8_t *mode
   return 0;
 }
 
-int mip_angular_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes, const uint8_t *modes,
-                       int nmodes, int32_t *d_cost, int32_t *d_sad, int32_t *d_satd, uint8_t *d_ang_mode, int32_t *d_ang_cost,
-                       int32_t bias, uint8_t *d_best_mode, int32_t *d_best_cost, void *stream) {
+// Both device entry points: refine == false is mip_angular_device (seeds and d_tried not looked
+// at), refine == true mip_angular_refine_device.
+static int angular_device_impl(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes, const uint8_t *modes,
+                               int nmodes, bool refine, int seeds, int32_t *d_cost, int32_t *d_sad, int32_t *d_satd,
+                               uint8_t *d_ang_mode, int32_t *d_ang_cost, uint8_t *d_tried, int32_t bias, uint8_t *d_best_mode,
+                               int32_t *d_best_cost, void *stream) {
   if (!e) return fail("engine is NULL");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   if (!d_frames) return fail("bad angular arguments: no frames");
   mipgpu::AngList list;
-  if (angular_args_ok(e, nframes, modes, nmodes, d_cost || d_sad || d_satd || d_ang_mode || d_ang_cost || d_best_mode || d_best_cost,
+  if (angular_args_ok(e, nframes, modes, nmodes,
+                      d_cost || d_sad || d_satd || d_ang_mode || d_ang_cost || d_best_mode || d_best_cost || (refine && d_tried),
                       &list) != 0)
     return -1;
+  if (refine && !mipgpu::ang_seeds_ok(seeds)) return fail("angular: seeds must be 1..%d", MIP_ANGULAR_MAX_SEEDS);
   if (!d_ang_mode != !d_ang_cost) return fail("angular: d_ang_mode and d_ang_cost are given together");
   if (!d_best_mode != !d_best_cost) return fail("angular: d_best_mode and d_best_cost are given together");
   if (!mipgpu::ang_bias_ok(bias)) return fail("angular: the bias is outside 0..%d", (int)mipgpu::kAngMaxBias);
@@ -1504,7 +1509,7 @@ int mip_angular_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *
   const uint16_t *refs = nullptr;
   bool engine_refs = false;
   if (intra_reference_source(e, d_frames, d_refs, nframes, s, &refs, &engine_refs) != 0) return -1;
-  mipgpu::AngularArgs a{};
+  mipgpu::AngularRefineArgs a{};  // (the plain launch takes its AngularArgs part)
   a.orig = d_frames;
   a.refs = refs;
   a.unavail = e->d_pred_unavail[engine_refs ? 1 : 0];
@@ -1526,22 +1531,48 @@ int mip_angular_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *
   a.nmodes = list.n;
   for (int k = 0; k < 3; k++) a.listed[k] = list.listed[k];
   for (int q = 0; q < list.n; q++) a.modes[q] = list.packed[q];
-  HIP_TRY(mipgpu::launch_angular(a, s));
+  if (refine) {
+    a.tried = d_tried;
+    a.nseeds = std::min(seeds, list.n);
+    for (int m = MIP_ANGULAR_FIRST; m <= MIP_ANGULAR_LAST; m++) a.all[m - MIP_ANGULAR_FIRST] = mipgpu::ang_pack(m);
+    HIP_TRY(mipgpu::launch_angular_refine(a, s));
+  } else {
+    HIP_TRY(mipgpu::launch_angular(a, s));
+  }
   return intra_reference_done(e, engine_refs, s);
+}
+
+int mip_angular_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes, const uint8_t *modes,
+                       int nmodes, int32_t *d_cost, int32_t *d_sad, int32_t *d_satd, uint8_t *d_ang_mode, int32_t *d_ang_cost,
+                       int32_t bias, uint8_t *d_best_mode, int32_t *d_best_cost, void *stream) {
+  return angular_device_impl(e, d_frames, d_refs, nframes, modes, nmodes, false, 0, d_cost, d_sad, d_satd, d_ang_mode, d_ang_cost,
+                             nullptr, bias, d_best_mode, d_best_cost, stream);
+}
+
+int mip_angular_refine_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes, const uint8_t *modes,
+                              int nmodes, int seeds, int32_t *d_cost, int32_t *d_sad, int32_t *d_satd, uint8_t *d_ang_mode,
+                              int32_t *d_ang_cost, uint8_t *d_ang_tried, int32_t bias, uint8_t *d_best_mode, int32_t *d_best_cost,
+                              void *stream) {
+  return angular_device_impl(e, d_frames, d_refs, nframes, modes, nmodes, true, seeds, d_cost, d_sad, d_satd, d_ang_mode, d_ang_cost,
+                             d_ang_tried, bias, d_best_mode, d_best_cost, stream);
 }
 
 // With cost_out the chunk is cut so that the call's device table stays within this bound (one
 // frame at least): a 1080p frame's table is 189 MB.
 static constexpr size_t kAngularTableBytes = (size_t)256 << 20;
 
-int mip_angular_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes, const uint8_t *modes,
-                       int nmodes, int32_t *cost_out, uint8_t *ang_mode_out, int32_t *ang_cost_out) {
+// Both host calls (refine as in angular_device_impl).
+static int angular_frames_impl(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes, const uint8_t *modes,
+                               int nmodes, bool refine, int seeds, int32_t *cost_out, uint8_t *ang_mode_out, int32_t *ang_cost_out,
+                               uint8_t *tried_out) {
   if (!e) return fail("engine is NULL");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   if (!frames) return fail("bad angular arguments: no frames");
   mipgpu::AngList list;
-  if (angular_args_ok(e, nframes, modes, nmodes, cost_out || ang_mode_out || ang_cost_out, &list) != 0) return -1;
+  if (angular_args_ok(e, nframes, modes, nmodes, cost_out || ang_mode_out || ang_cost_out || (refine && tried_out), &list) != 0) return -1;
   if (!ang_mode_out != !ang_cost_out) return fail("angular: ang_mode_out and ang_cost_out are given together");
+  if (refine && !mipgpu::ang_seeds_ok(seeds)) return fail("angular: seeds must be 1..%d", MIP_ANGULAR_MAX_SEEDS);
+  if (!refine) tried_out = nullptr;
   HIP_TRY(hipSetDevice(e->device));
   if (quiesce(e) != 0) return -1;  // (host searches in flight use the engine buffers)
   const size_t fs = (size_t)e->width * e->height, mb = (size_t)e->opts.max_batch, ncu = (size_t)e->nctus * MIP_CUS_PER_CTU;
@@ -1551,9 +1582,9 @@ int mip_angular_frames(mip_engine *e, const uint16_t *frames, const uint16_t *re
   // the call's own device buffers (through the device block cache)
   uint16_t *t_refs = nullptr;
   int32_t *d_cost = nullptr, *d_ang_cost = nullptr;
-  uint8_t *d_ang_mode = nullptr;
+  uint8_t *d_ang_mode = nullptr, *d_tried = nullptr;
   auto done = [&](int rc) {
-    for (void *p : {(void *)t_refs, (void *)d_cost, (void *)d_ang_cost, (void *)d_ang_mode}) dev_free(p);
+    for (void *p : {(void *)t_refs, (void *)d_cost, (void *)d_ang_cost, (void *)d_ang_mode, (void *)d_tried}) dev_free(p);
     return rc;
   };
 #define ANG_TRY(expr)                                                                      \
@@ -1574,15 +1605,17 @@ int mip_angular_frames(mip_engine *e, const uint16_t *frames, const uint16_t *re
     ANG_TRY(dev_malloc(e->device, (void **)&d_ang_cost, chunk * ncu * sizeof(int32_t)));
     ANG_TRY(dev_malloc(e->device, (void **)&d_ang_mode, chunk * ncu));
   }
+  if (tried_out) ANG_TRY(dev_malloc(e->device, (void **)&d_tried, chunk * ncu));
   hipStream_t s = e->stream;
   for (size_t f0 = 0; f0 < (size_t)nframes; f0 += chunk) {
     const size_t nb = std::min(chunk, (size_t)nframes - f0);
     ANG_TRY(hipMemcpyAsync(e->d_frames, frames + f0 * fs, nb * fs * 2, hipMemcpyHostToDevice, s));
     if (d_refs) ANG_TRY(hipMemcpyAsync(d_refs, refs_or_null + f0 * fs, nb * fs * 2, hipMemcpyHostToDevice, s));
     // (without references the device entry point filters the frames itself when the engine has a filter)
-    if (mip_angular_device(e, e->d_frames, d_refs, (int)nb, modes, nmodes, d_cost, nullptr, nullptr, d_ang_mode, d_ang_cost, 0,
-                           nullptr, nullptr, s) != 0)
+    if (angular_device_impl(e, e->d_frames, d_refs, (int)nb, modes, nmodes, refine, seeds, d_cost, nullptr, nullptr, d_ang_mode,
+                            d_ang_cost, d_tried, 0, nullptr, nullptr, s) != 0)
       return done(-1);
+    if (tried_out) ANG_TRY(hipMemcpyAsync(tried_out + f0 * ncu, d_tried, nb * ncu, hipMemcpyDeviceToHost, s));
     if (cost_out) ANG_TRY(hipMemcpyAsync(cost_out + f0 * entries, d_cost, nb * entries * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (ang_cost_out) {
       ANG_TRY(hipMemcpyAsync(ang_cost_out + f0 * ncu, d_ang_cost, nb * ncu * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -1593,6 +1626,18 @@ int mip_angular_frames(mip_engine *e, const uint16_t *frames, const uint16_t *re
 #undef ANG_TRY
   e->refs_pending = false;
   return done(0);
+}
+
+int mip_angular_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes, const uint8_t *modes,
+                       int nmodes, int32_t *cost_out, uint8_t *ang_mode_out, int32_t *ang_cost_out) {
+  return angular_frames_impl(e, frames, refs_or_null, nframes, modes, nmodes, false, 0, cost_out, ang_mode_out, ang_cost_out, nullptr);
+}
+
+int mip_angular_refine_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes, const uint8_t *modes,
+                              int nmodes, int seeds, int32_t *cost_out, uint8_t *ang_mode_out, int32_t *ang_cost_out,
+                              uint8_t *tried_out) {
+  return angular_frames_impl(e, frames, refs_or_null, nframes, modes, nmodes, true, seeds, cost_out, ang_mode_out, ang_cost_out,
+                             tried_out);
 }
 
 double mip_time_search_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes,

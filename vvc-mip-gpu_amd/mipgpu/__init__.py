@@ -66,6 +66,8 @@ MODE_DC = 0xF1                             # merge of intra_device (regular intr
 INTRA_MAX_BIAS = 1 << 20                   # biases of that merge: 0 .. 1<<20
 MODE_ANGULAR_BASE = 0x80                   # MIP_MODE_ANGULAR(m) = 0x80 + m: best_mode value of angular mode m (2..66)
 ANGULAR_MODES = 65                         # MIP_ANGULAR_MODES: slots of the angular tables, slot = m - 2
+ANGULAR_MAX_SEEDS = 3                      # MIP_ANGULAR_MAX_SEEDS: seeds of angular_refine are 1..3
+ANGULAR_EVEN_MODES = tuple(range(2, 67, 2))   # the 33 even modes: the usual coarse list of angular_refine
 PRED_REGULAR = 1                           # MIP_PRED_REGULAR: flags bit of predict(..., regular=True)
 PRED_ANGULAR = 4                           # MIP_PRED_ANGULAR: flags bit of predict(..., angular=True)
 CHAIN_ANGULAR = 1                          # MIP_CHAIN_ANGULAR: flags bit of mip_predicted_frames_ex (the angular stage)
@@ -160,6 +162,8 @@ def library():
         "mip_intra_frames": (ip, [vp, vp, vp, ip, vp, vp, vp]),
         "mip_angular_device": (ip, [vp, vp, vp, ip, vp, ip, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp]),
         "mip_angular_frames": (ip, [vp, vp, vp, ip, vp, ip, vp, vp, vp]),
+        "mip_angular_refine_device": (ip, [vp, vp, vp, ip, vp, ip, ip, vp, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp]),
+        "mip_angular_refine_frames": (ip, [vp, vp, vp, ip, vp, ip, ip, vp, vp, vp, vp]),
         "mip_time_search_device": (ctypes.c_double, [vp, vp, vp, ip, vp, ip]),
         "mip_host_stats": (ip, [vp, ctypes.POINTER(ctypes.c_uint64), ip]),
         "mip_search_census": (ip, [vp, ctypes.POINTER(ctypes.c_uint64), ip]),
@@ -641,6 +645,51 @@ class MipEngine:
                                                 _ptr(cost), _ptr(sad), _ptr(satd), _ptr(ang_mode), _ptr(ang_cost), int(bias),
                                                 _ptr(best_mode), _ptr(best_cost), ctypes.c_void_p(s.cuda_stream)))
 
+    def angular_refine(self, frames, refs=None, modes=None, seeds=1, table=False) -> dict:
+        """Coarse-to-fine angular search of host frames (mip_angular_refine_frames): every CU ranks
+        `modes` (see angular; the usual coarse list is ANGULAR_EVEN_MODES) and also evaluates the
+        +-1 neighbours, inside 2..66 and not in the list, of its own `seeds` (1..3) best modes.
+        dict of 'ang_mode' / 'ang_cost' (the best of everything evaluated, ties to the lower mode),
+        'tried' uint8 [F, nCTUs*5380] (modes evaluated per CU, 0 for unavailable CUs) and, with
+        `table`, 'cost' (slots of modes not evaluated for a CU are UNAVAILABLE)."""
+        f = self._frames(frames)
+        r = None if refs is None else self._frames(refs)
+        n = f.shape[0]
+        m = _modes(modes)
+        res = {"ang_mode": np.empty((n, self.cus_per_frame), np.uint8), "ang_cost": np.empty((n, self.cus_per_frame), np.int32),
+               "tried": np.empty((n, self.cus_per_frame), np.uint8)}
+        if table:
+            res["cost"] = np.empty((n, self.cus_per_frame, ANGULAR_MODES), np.int32)
+        with self._lock:
+            _check(library().mip_angular_refine_frames(self._h, _ptr(f), _ptr(r), n, _ptr(m), 0 if m is None else m.size, _seeds(seeds),
+                                                       _ptr(res.get("cost")), _ptr(res["ang_mode"]), _ptr(res["ang_cost"]),
+                                                       _ptr(res["tried"])))
+        return res
+
+    def angular_refine_device(self, frames, modes=None, seeds=1, cost=None, sad=None, satd=None, ang_mode=None, ang_cost=None,
+                              tried=None, refs=None, bias=0, best_mode=None, best_cost=None, stream=None):
+        """Asynchronous coarse-to-fine angular search and decision merge on device tensors
+        (mip_angular_refine_device): angular_device's arguments and outputs over the modes each CU
+        evaluated -- the list plus the neighbours of its `seeds` best modes, see angular_refine --
+        and `tried` uint8 [F, nCTUs*5380], the count of those modes.  At least one output."""
+        import torch
+        n = frames.shape[0]
+        m = _modes(modes)
+        want = {"cost": (cost, 4 * ANGULAR_MODES), "sad": (sad, 4 * ANGULAR_MODES), "satd": (satd, 4 * ANGULAR_MODES),
+                "ang_mode": (ang_mode, 1), "ang_cost": (ang_cost, 4), "tried": (tried, 1), "best_mode": (best_mode, 1),
+                "best_cost": (best_cost, 4)}
+        for name, (t, size) in want.items():
+            if t is not None and (t.numel() * t.element_size() != n * self.cus_per_frame * size or not t.is_contiguous()):
+                raise MipError(f"angular_refine_device: {name} must be a contiguous tensor of {n * self.cus_per_frame * size} bytes")
+        if int(bias) != np.clip(int(bias), -(1 << 31), (1 << 31) - 1):
+            raise MipError("bias does not fit int32")
+        s = stream if stream is not None else torch.cuda.current_stream(frames.device)
+        with self._lock:
+            _check(library().mip_angular_refine_device(self._h, _ptr(frames), _ptr(refs), n, _ptr(m), 0 if m is None else m.size,
+                                                       _seeds(seeds), _ptr(cost), _ptr(sad), _ptr(satd), _ptr(ang_mode), _ptr(ang_cost),
+                                                       _ptr(tried), int(bias), _ptr(best_mode), _ptr(best_cost),
+                                                       ctypes.c_void_p(s.cuda_stream)))
+
     def time_search_device(self, frames, costs, refs=None, reps=10) -> float:
         with self._lock:
             ms = library().mip_time_search_device(self._h, _ptr(frames), _ptr(refs), frames.shape[0], _ptr(costs),
@@ -752,6 +801,13 @@ def _modes(modes):
     return np.ascontiguousarray(m, dtype=np.uint8)
 
 
+def _seeds(seeds):
+    """seeds of angular_refine as the C int (the library checks the range 1..ANGULAR_MAX_SEEDS)."""
+    if int(seeds) != seeds or int(seeds) != np.clip(int(seeds), -(1 << 31), (1 << 31) - 1):
+        raise MipError("seeds must be an integer in 1..%d" % ANGULAR_MAX_SEEDS)
+    return int(seeds)
+
+
 def partition_device(best_cost, width, height, penalty=None, best_mode=None, leaf=None, ctu_cost=None, ctu_leaves=None,
                      items=None, stream=None):
     """CTU partition decision on device tensors (mip_partition_device, contract in
@@ -796,6 +852,6 @@ def filter_device(frames_in, frames_out, filter, kernel_idx=0, stream=None):
     return frames_out
 
 
-__all__ = ["MODE_PLANAR", "MODE_DC", "INTRA_MAX_BIAS", "MODE_ANGULAR_BASE", "ANGULAR_MODES", "PRED_REGULAR", "PRED_ANGULAR", "CHAIN_ANGULAR", "PRED_ITEM", "PRED_NONE", "pred_items", "PART_MAX_LEAVES", "PART_MAX_PENALTY", "partition_device", "MipEngine", "MipError", "build_id", "source_id", "FILTERS", "FILTER_NONE", "filter_index", "filter_device", "topk_device", "library",
+__all__ = ["MODE_PLANAR", "MODE_DC", "INTRA_MAX_BIAS", "MODE_ANGULAR_BASE", "ANGULAR_MODES", "ANGULAR_MAX_SEEDS", "ANGULAR_EVEN_MODES", "PRED_REGULAR", "PRED_ANGULAR", "CHAIN_ANGULAR", "PRED_ITEM", "PRED_NONE", "pred_items", "PART_MAX_LEAVES", "PART_MAX_PENALTY", "partition_device", "MipEngine", "MipError", "build_id", "source_id", "FILTERS", "FILTER_NONE", "filter_index", "filter_device", "topk_device", "library",
            "pinned_empty", "unavailable_cus", "numa_node", "bind_thread", "device_cache", "copy_device",
            "layout", "SHAPES", "COSTS_PER_CTU", "CUS_PER_CTU", "UNAVAILABLE", "num_ctus"]
