@@ -13,6 +13,8 @@
 //     those lines with the HIP calls and getenv replaced by arguments (the ring's footprint:
 //     bytes rounded up to 4096, its default alignment) and printed the same rows in the same
 //     order.
+//  d. stage_chunk_frames (the stage wrappers' walk): max_batch, the call's frames and the
+//     angular table bound, each where it decides, from the rule written out by hand.
 #include <stdint.h>
 
 #include <cstdio>
@@ -285,11 +287,30 @@ static void test_chunks() {
   CHECK(ring_piece_bytes(kSigBestCost | kSigDec, 3, tiny) == (size_t)3 * MIP_CUS_PER_CTU * 4, "best costs: four bytes per CU");
 }
 
+static void test_stage_chunk_frames() {
+  CHECK(stage_chunk_frames(200, 3, 0) == 3, "fewer frames than max_batch: the call's frames");
+  CHECK(stage_chunk_frames(2, 3, 0) == 2, "more frames than max_batch: max_batch");
+  CHECK(stage_chunk_frames(2, 2, 0) == 2 && stage_chunk_frames(1, 1, 0) == 1, "no bound");
+  CHECK(stage_chunk_frames(8, 5, kAngularTableBytes / 5) == 5 && stage_chunk_frames(8, 5, kAngularTableBytes / 4) == 4,
+        "the table bound cuts only where it is the smaller");
+  CHECK(stage_chunk_frames(4, 3, kAngularTableBytes + 1) == 1 && stage_chunk_frames(4, 3, (size_t)1 << 40) == 1,
+        "a bound below one frame's table: one frame");
+  // one CTU's angular cost table: 5380 CUs x 65 modes x int32; 268435456 / 1398800 = 191.9
+  static_assert(MIP_CUS_PER_CTU == 5380 && kAngularTableBytes == 268435456, "the figures of this case");
+  const size_t table = (size_t)MIP_CUS_PER_CTU * 65 * 4;
+  CHECK(table == 1398800, "%zu", table);
+  for (int n : {191, 192, 200, 1000})
+    CHECK(stage_chunk_frames(200, n, table) == 191, "%d frames on max_batch 200: %d, want 191", n,
+          stage_chunk_frames(200, n, table));
+  CHECK(stage_chunk_frames(200, 190, table) == 190 && stage_chunk_frames(100, 200, table) == 100, "below the bound");
+}
+
 int main() {
   test_call_sig();
   test_merge_cap();
   test_merge_decision();
   test_chunks();
+  test_stage_chunk_frames();
   if (fails) return 1;
   std::printf("host_policy: ok\n");
   return 0;

@@ -46,6 +46,21 @@ def test_filters_at_every_residue(gpu_available, p):
                     assert np.array_equal(got, want), (filt, k, kind, np.argwhere(got != want)[:4])
 
 
+def test_filter_frames_beyond_max_batch(gpu_available):
+    """More frames than max_batch in one eng.filter_frames call (3 distinct frames on an engine
+    of 2: a chunk of two and a chunk of one), with one separable and one 2-D filter: every
+    frame of the output equals the oracle's filter of that frame."""
+    w, h = 136, 72
+    frames = np.stack([S.content("noise", w, h, salt) for salt in (0, 1, 2)])
+    assert not np.array_equal(frames[0], frames[1]) and not np.array_equal(frames[1], frames[2])
+    with MipEngine(w, h, max_batch=2) as eng:
+        for filt in (S.SEP[0], S.TWO_D[0]):
+            got = eng.filter_frames(frames, filt, 0)
+            assert got.shape == frames.shape
+            for f in range(3):
+                assert np.array_equal(got[f], O.filter_frame(frames[f], filt, 0)), (filt, f)
+
+
 # Widths that are no multiple of 4 (the engine refuses them, the module-level filter does not):
 # the only ones at which a 2-D filter's left / right halo gate `qx + tc < W - 1` (tap_valid) has
 # its boundary case qx + tc == W - 1 -- halo columns are qx + 128 and qx + 129 -- and, at

@@ -61,7 +61,7 @@ def test_the_mip_kernel_and_its_launcher_are_left_alone():
     assert "pred_decode<REGULAR, false>(a, it, PredShapes{})" in mip and "pred_decode<false, true>(a, a.items[idx], AngShapes{})" in ang
     for text in (mip, ang):
         assert '#include "predict_rule.h"' in text and "it.pitch <" not in text    # no copy of the rule
-    with open(os.path.join(L.CSRC, "mipgpu.cpp")) as f:
+    with open(os.path.join(L.CSRC, "host_stages.cpp")) as f:
         host = f.read()
     launch = host[host.index("static int predict_launch("):host.index("static int predict_args_ok(")]
     assert launch.index("launch_predict(a, s)") < launch.index("if (flags & MIP_PRED_ANGULAR)") < launch.index("launch_predict_angular(a, s)")

@@ -1,6 +1,7 @@
-// engine.h -- private to the library: the engine's state and what its two translation units
-// share (mipgpu.cpp: create / destroy, block cache, device API, prediction, partition, intra;
-// host_pipeline.cpp: the host API's pipeline).
+// engine.h -- private to the library: the engine's state and what its three translation units
+// share (mipgpu.cpp: create / destroy, block cache, the search's device API, the filter;
+// host_pipeline.cpp: the host API's pipeline; host_stages.cpp: prediction, partition and intra
+// costs, device entry points and chunked host wrappers).
 #pragma once
 #include "mipgpu.h"
 
@@ -9,6 +10,8 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -219,10 +222,37 @@ struct mip_engine {
   std::recursive_mutex mu;
 };
 
+// CU count limit of one launch (int32 indices in the decision-list kernel).
+constexpr long long kMaxCus = (1LL << 31) - 256;
+
 // ---- mipgpu.cpp ----
 // hipMalloc / hipFree through the device block cache.
 hipError_t dev_malloc(int device, void **p, size_t bytes);
 void dev_free(void *p);
+// The device blocks of one call: taken from dev_malloc, given back when the call returns,
+// whichever way.  (Blocks that outlive the call -- the engine's buffers and tables -- are not
+// taken through it.)
+struct DevScratch {
+  const int device;
+  std::vector<void *> blocks;
+  explicit DevScratch(int d) : device(d) {}
+  DevScratch(const DevScratch &) = delete;
+  ~DevScratch() {
+    for (void *p : blocks) dev_free(p);
+  }
+  template <class T>
+  hipError_t take(T *&p, size_t bytes) {  // p is set only on success
+    void *b = nullptr;
+    const hipError_t err = dev_malloc(device, &b, bytes);
+    if (err == hipSuccess) blocks.push_back(p = static_cast<T *>(b));
+    return err;
+  }
+};
+// Engine-filtered references of a device-API stage: before its kernels (*refs: what they read;
+// *engine_refs: the engine's reference scratch, filtered from d_frames on s) and after them.
+int engine_refs_begin(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes, hipStream_t s,
+                      const uint16_t **refs, bool *engine_refs);
+int engine_refs_end(mip_engine *e, bool engine_refs, hipStream_t s);
 // caller_refs: d_refs holds caller-supplied reference frames (checked against the 10-bit
 // contract like the frames; engine-filtered references are not: the separable filters'
 // defined > 10-bit outputs at the last columns go to the fixup kernel).
@@ -233,10 +263,26 @@ int search_device_impl(mip_engine *e, const uint16_t *d_frames, const uint16_t *
                        uint32_t *const *frame_status = nullptr, bool alternating = false);
 // Status sets (mip_engine::h_status).  take_status: read and clear a set: 0, or 1 (frame
 // samples) | 2 (reference samples); contract_error: fail() with the violation's text;
-// check_device_status: the device API's set.
+// check_device_status: the device API's set; device_status: its device pointer.
 uint32_t take_status(mip_engine *e, int set);
 int contract_error(uint32_t flags, const char *what);
 int check_device_status(mip_engine *e);
+uint32_t *device_status(mip_engine *e);
+
+// ---- host_stages.cpp ----
+// A host call's frames through the engine buffers, `chunk` frames (host_policy.h
+// stage_chunk_frames) at a time on e->stream: the chunk's frames are uploaded into e->d_frames --
+// and its caller references, if any, into a device buffer handed to the body -- then
+// body(frames of the chunk, d_refs or null) launches the device stage, the outputs asked for
+// are downloaded and the stream is synchronised.  Clears refs_pending: nothing reads d_refs
+// after the last synchronise.
+struct ChunkOut {
+  void *host;       // the call's output buffer for all its frames; null: not asked for
+  const void *dev;  // the device buffer the body fills for a chunk
+  size_t bytes;     // per frame
+};
+int walk_chunks(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes, int chunk,
+                std::initializer_list<ChunkOut> outs, const std::function<int(int, const uint16_t *)> &body);
 
 // ---- host_pipeline.cpp ----
 // Launch the engine's open (merged) chunk, if any.

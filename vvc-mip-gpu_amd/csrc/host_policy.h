@@ -1,5 +1,6 @@
 // host_policy.h -- what the host pipeline (host_pipeline.cpp) decides, as arithmetic: a call's
-// signature, whether it joins or opens a merged chunk, and the chunk sizes of a chunked call.
+// signature, whether it joins or opens a merged chunk, and the chunk sizes of a chunked call --
+// and the chunk size of the stage wrappers' walk (host_stages.cpp).
 // No HIP dependency and no environment reads (knob values are arguments); unit-tested by
 // tests/cpp/test_host_policy.cpp.
 #pragma once
@@ -209,6 +210,18 @@ inline std::vector<int> call_chunks(const ChunkCall &c, int sb, int nslots, cons
   const bool ramps = nslots == 4 && sb >= 16 && ramp != kRampOff;
   return chunk_plan(c.nframes, sb, ramps && c.idle && c.nframes >= 2 * sb,
                     ramps && c.sync && !download_bytes(c.sig, b) && ramp != kRampUp, nhead, ntail);
+}
+
+// ---- Stage wrappers (host_stages.cpp walk_chunks) ----
+// Frames per chunk of a stage wrapper's walk: what the engine buffers hold (max_batch), and for
+// a call with a per-frame device table of table_bytes_per_frame (0: none) as many frames as keep
+// that table within kAngularTableBytes, one at least: a 1080p frame's angular cost table is
+// 189 MB.
+constexpr size_t kAngularTableBytes = (size_t)256 << 20;
+inline int stage_chunk_frames(int max_batch, int nframes, size_t table_bytes_per_frame) {
+  const int chunk = std::min(max_batch, nframes);
+  if (!table_bytes_per_frame) return chunk;
+  return (int)std::max<size_t>(1, std::min((size_t)chunk, kAngularTableBytes / table_bytes_per_frame));
 }
 
 }  // namespace mipgpu

@@ -1,7 +1,8 @@
 // mipgpu.cpp -- C-ABI engine (include/mipgpu.h): device set-up, buffers, the upload of the
-// planned work lists (work_plan.h), the device API's launch sequence, prediction, partition and
-// the Planar / DC baseline costs.
-// The host API's pipeline, which replaces main.cpp's OpenCL host loop: host_pipeline.cpp.
+// planned work lists (work_plan.h), the search's device API with its launch sequence, and the
+// filter.
+// The host API's pipeline, which replaces main.cpp's OpenCL host loop: host_pipeline.cpp; the
+// stages behind the search (prediction, partition, intra costs): host_stages.cpp.
 #include "engine.h"
 
 #include <algorithm>
@@ -11,10 +12,6 @@
 #include <cstring>
 
 #include "mip_tables.h"
-#include "angular_plan.h"
-#include "intra_plan.h"
-#include "partition_plan.h"
-#include "predict_rule.h"
 
 thread_local std::string g_err;
 
@@ -81,9 +78,6 @@ bool filter_valid(int f, int k) {
   const bool five = f >= 4;
   return k >= 0 && k < (five ? 3 : 5);
 }
-
-// CU count limit of one launch (int32 indices in the decision-list kernel).
-constexpr long long kMaxCus = (1LL << 31) - 256;
 
 // MIPGPU_PIPE_KERNEL (A/B knob) for the host pipeline's chunks: 4 (default) = the four-wave
 // twin for small alternating chunks and for decisions-only chunks, 8 = the twin for every
@@ -169,7 +163,7 @@ int check_device_status(mip_engine *e) {
 }
 
 // Device pointers of the status sets the kernels mark.
-static uint32_t *device_status(mip_engine *e) { return e->d_status + (size_t)mip_engine::kCallRing * mipgpu::kStatusWords; }
+uint32_t *device_status(mip_engine *e) { return e->d_status + (size_t)mip_engine::kCallRing * mipgpu::kStatusWords; }
 
 // Device block cache (round 6).  Freeing a large device allocation halves every later
 // host <-> device copy of the process on this platform -- 56.4 -> 28.7 GB/s, SDMA and blit
@@ -608,6 +602,33 @@ int mip_filter_device(const uint16_t *d_in, uint16_t *d_out, int width, int heig
 
 }  // extern "C"
 
+// The reference frames of a device-API stage (search, prediction, intra costs): the caller's,
+// the originals, or -- *engine_refs -- the engine's filter applied into the engine's reference
+// scratch, ordered after that scratch's previous users: this is the rule that keeps two writers
+// of d_refs on different streams apart (mip_engine::refs_done).  The stage then records refs_done
+// behind its last kernel that reads the scratch (engine_refs_end).
+int engine_refs_begin(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes, hipStream_t s,
+                      const uint16_t **refs, bool *engine_refs) {
+  *refs = d_refs ? d_refs : d_frames;
+  *engine_refs = !d_refs && e->opts.filter != MIP_FILTER_NONE;
+  if (!*engine_refs) return 0;
+  if (nframes > e->opts.max_batch) return fail("nframes %d > max_batch %d", nframes, e->opts.max_batch);
+  if (e->refs_pending) HIP_TRY(hipStreamWaitEvent(s, e->refs_done, 0));  // last reader of d_refs
+  if (e->host_pending)  // host calls in flight (calls complete in order: the last one)
+    HIP_TRY(hipStreamWaitEvent(s, e->call_done[(e->host_calls - 1) % mip_engine::kCallRing], 0));
+  if (mip_filter_device(d_frames, e->d_refs, e->width, e->height, nframes, e->opts.filter, e->opts.kernel_idx, s) != 0)
+    return -1;
+  *refs = e->d_refs;
+  return 0;
+}
+int engine_refs_end(mip_engine *e, bool engine_refs, hipStream_t s) {
+  if (engine_refs) {
+    HIP_TRY(hipEventRecord(e->refs_done, s));
+    e->refs_pending = true;
+  }
+  return 0;
+}
+
 int search_device_impl(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes, int32_t *d_costs,
                        int32_t *d_sad, int32_t *d_satd, uint8_t *d_best, int32_t *d_best_cost, hipStream_t s,
                        bool caller_refs, uint32_t *d_status, int ctu0, int nrange, uint32_t *split_acc,
@@ -628,22 +649,13 @@ int search_device_impl(mip_engine *e, const uint16_t *d_frames, const uint16_t *
     return fail("CTU range [%d, %d) outside the frame's %d CTUs", ctu0, ctu0 + nrange, e->nctus);
   const long long total_cus = (long long)nframes * e->nctus * MIP_CUS_PER_CTU;
   if (total_cus > kMaxCus) return fail("%d frames x %d CTUs exceed %lld CUs per launch", nframes, e->nctus, kMaxCus);
-  const uint16_t *refs = d_refs;
-  const bool engine_refs = !refs && e->opts.filter != MIP_FILTER_NONE;
-  if (engine_refs) {
-    if (nframes > e->opts.max_batch) return fail("nframes %d > max_batch %d", nframes, e->opts.max_batch);
-    if (e->refs_pending) HIP_TRY(hipStreamWaitEvent(s, e->refs_done, 0));  // last reader of d_refs
-    if (e->host_pending)  // host calls in flight (calls complete in order: the last one)
-      HIP_TRY(hipStreamWaitEvent(s, e->call_done[(e->host_calls - 1) % mip_engine::kCallRing], 0));
-    if (mip_filter_device(d_frames, e->d_refs, e->width, e->height, nframes, e->opts.filter,
-                          e->opts.kernel_idx, s) != 0)
-      return -1;
-    refs = e->d_refs;
-  }
-  const bool alt = refs != nullptr && refs != d_frames;
+  const uint16_t *refs = nullptr;
+  bool engine_refs = false;
+  if (engine_refs_begin(e, d_frames, d_refs, nframes, s, &refs, &engine_refs) != 0) return -1;
+  const bool alt = refs != d_frames;
   mipgpu::SearchArgs a{};
   a.orig = d_frames;
-  a.refs = alt ? refs : d_frames;
+  a.refs = refs;
   a.cost = d_costs;
   a.best_mode = decisions_only ? d_best : nullptr;
   a.best_cost = decisions_only ? d_best_cost : nullptr;
@@ -758,10 +770,7 @@ int search_device_impl(mip_engine *e, const uint16_t *d_frames, const uint16_t *
   }
   if (ring.launched(slot, s) != 0) return fail("hipEventRecord failed");
   if (alt && e->nfixup[map]) HIP_TRY(mipgpu::launch_fixup(a, e->d_fixup[map], e->nfixup[map], nframes, s));
-  if (engine_refs) {
-    HIP_TRY(hipEventRecord(e->refs_done, s));
-    e->refs_pending = true;
-  }
+  if (engine_refs_end(e, engine_refs, s) != 0) return -1;
   if (timing) {
     HIP_TRY(hipMemcpyAsync(clocks.data(), a.wave_clock, clocks.size() * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -885,759 +894,13 @@ int mip_filter_frames(mip_engine *e, const uint16_t *frames, int nframes, int fi
   if (quiesce(e) != 0) return -1;  // (host searches in flight use d_frames / d_refs)
   const size_t fs = (size_t)e->width * e->height;
   if (!e->d_refs) HIP_TRY(dev_malloc(e->device, (void **)&e->d_refs, fs * e->hp_frames * 2));
-  for (int f0 = 0; f0 < nframes; f0 += e->opts.max_batch) {
-    const int nb = std::min(e->opts.max_batch, nframes - f0);
-    HIP_TRY(hipMemcpyAsync(e->d_frames, frames + f0 * fs, nb * fs * 2, hipMemcpyHostToDevice, e->stream));
-    if (mip_filter_device(e->d_frames, e->d_refs, e->width, e->height, nb, filter, kernel_idx, e->stream) != 0)
-      return -1;
-    HIP_TRY(hipMemcpyAsync(out + f0 * fs, e->d_refs, nb * fs * 2, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-  }
+  const int chunk = mipgpu::stage_chunk_frames(e->opts.max_batch, nframes, 0);
+  auto filter_chunk = [&](int nb, const uint16_t *) {
+    return mip_filter_device(e->d_frames, e->d_refs, e->width, e->height, nb, filter, kernel_idx, e->stream);
+  };
+  if (walk_chunks(e, frames, nullptr, nframes, chunk, {{out, e->d_refs, fs * 2}}, filter_chunk) != 0) return -1;
   HIP_TRY(hipStreamSynchronize(e->stream2));
-  e->refs_pending = false;
   return 0;
-}
-
-// ---------------------------------------------------------------- prediction output
-int mip_pred_layout(int width, int height, int nframes, int layout, mip_pred_item *items, int64_t n,
-                    int64_t *out_samples) {
-  if (width <= 0 || height <= 0 || width % 4 || height % 4 || nframes < 1 || n < 0 || (n && !items) || !out_samples)
-    return fail("bad prediction-layout arguments");
-  if (layout != MIP_PRED_PACKED && layout != MIP_PRED_FRAME) return fail("unknown prediction layout %d", layout);
-  const std::vector<mipgpu::CuGeo> &geo = mipgpu::cu_geo_table();
-  const int cols = (width + 127) / 128, ncus = mip_num_ctus(width, height) * MIP_CUS_PER_CTU;
-  const int64_t fs = (int64_t)width * height;
-  int64_t next = 0;
-  for (int64_t i = 0; i < n; i++) {
-    mip_pred_item &it = items[i];
-    if (it.frame < 0 || it.frame >= nframes)
-      return fail("prediction item %lld: frame %d outside 0..%d", (long long)i, it.frame, nframes - 1);
-    if (it.cu < 0 || it.cu >= ncus) return fail("prediction item %lld: cu %d outside 0..%d", (long long)i, it.cu, ncus - 1);
-    const int ctu = it.cu / MIP_CUS_PER_CTU;
-    const mipgpu::CuGeo &g = geo[(size_t)(it.cu % MIP_CUS_PER_CTU)];
-    const mip_shape_desc &sd = kShapes[g.shape];
-    if (layout == MIP_PRED_PACKED) {
-      it.pitch = sd.w;
-      it.offset = next;
-      next += (int64_t)sd.w * sd.h;
-    } else {
-      it.pitch = width;
-      it.offset = it.frame * fs + (int64_t)(128 * (ctu / cols) + g.y) * width + 128 * (ctu % cols) + g.x;
-    }
-  }
-  *out_samples = layout == MIP_PRED_PACKED ? next : (int64_t)nframes * fs;
-  return 0;
-}
-
-// The engine's prediction tables (mip_engine::d_pred_unavail, d_pred_geo), uploaded once.
-static int ensure_pred_tables(mip_engine *e) {
-  if (e->d_pred_geo) return 0;
-  const size_t ncus = (size_t)e->nctus * MIP_CUS_PER_CTU;
-  std::vector<uint8_t> un(ncus);
-  for (int m = 0; m < 2; m++) {
-    if (m == 1 && e->opts.filter == MIP_FILTER_NONE) {
-      e->d_pred_unavail[1] = e->d_pred_unavail[0];
-      break;
-    }
-    if (mip_unavailable_cus(e->width, e->height, m ? e->opts.filter : MIP_FILTER_NONE, un.data()) != 0) return -1;
-    HIP_TRY(dev_malloc(e->device, (void **)&e->d_pred_unavail[m], ncus));
-    HIP_TRY(hipMemcpy(e->d_pred_unavail[m], un.data(), ncus, hipMemcpyHostToDevice));
-  }
-  const std::vector<mipgpu::CuGeo> &geo = mipgpu::cu_geo_table();
-  std::vector<uint32_t> packed(geo.size());
-  for (size_t i = 0; i < geo.size(); i++) packed[i] = geo[i].shape | (uint32_t)geo[i].x << 8 | (uint32_t)geo[i].y << 16;
-  uint32_t *d = nullptr;
-  HIP_TRY(dev_malloc(e->device, (void **)&d, packed.size() * sizeof(uint32_t)));
-  if (hipMemcpy(d, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
-    dev_free(d);
-    return fail("uploading the CU geometry failed");
-  }
-  e->d_pred_geo = d;  // (set last: the tables are complete)
-  return 0;
-}
-
-// refs: the reference frames to predict from (already resolved); engine_refs: they are the
-// engine filter's output (its unavailable set applies).
-static int predict_launch(mip_engine *e, const uint16_t *refs, bool engine_refs, int nframes, const mip_pred_item *d_items,
-                          int64_t n, uint16_t *d_out, int64_t out_samples, uint32_t *d_skipped, unsigned flags, hipStream_t s) {
-  mipgpu::PredictArgs a{};
-  a.refs = refs;
-  a.items = d_items;
-  a.n = n;
-  a.unavail = e->d_pred_unavail[engine_refs ? 1 : 0];
-  a.geo = e->d_pred_geo;
-  a.out = d_out;
-  a.out_samples = out_samples;
-  a.skipped = d_skipped;
-  a.width = e->width;
-  a.height = e->height;
-  a.ctu_cols = e->ctu_cols;
-  a.nctus = e->nctus;
-  a.nframes = nframes;
-  a.refs_vec = (reinterpret_cast<uintptr_t>(refs) & 7) == 0;
-  a.regular = (flags & MIP_PRED_REGULAR) != 0;
-  HIP_TRY(mipgpu::launch_predict(a, s));
-  // MIP_PRED_ANGULAR: the kernel above has rejected and counted the angular items; the angular
-  // kernel emits them behind it and takes them off the count (final in stream order)
-  if (flags & MIP_PRED_ANGULAR) HIP_TRY(mipgpu::launch_predict_angular(a, s));
-  return 0;
-}
-
-static int predict_args_ok(const mip_engine *e, int nframes, const void *items, int64_t n, const void *out,
-                           int64_t out_samples, unsigned flags) {
-  if (!mipgpu::pred_flags_ok(flags)) return fail("unknown prediction flags 0x%x", flags);
-  if (nframes < 1 || n < 0 || out_samples < 0 || (n && (!items || !out))) return fail("bad prediction arguments");
-  if (n > kMaxCus) return fail("%lld prediction items exceed %lld per call", (long long)n, kMaxCus);
-  if ((long long)nframes * e->nctus * MIP_CUS_PER_CTU > kMaxCus) return fail("%d frames exceed %lld CUs per call", nframes, kMaxCus);
-  return 0;
-}
-
-int mip_predict_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes,
-                       const mip_pred_item *d_items, int64_t n, uint16_t *d_out, int64_t out_samples,
-                       uint32_t *d_skipped, void *stream) {
-  return mip_predict_device_ex(e, d_frames, d_refs, nframes, d_items, n, d_out, out_samples, d_skipped, 0, stream);
-}
-
-int mip_predict_device_ex(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes,
-                          const mip_pred_item *d_items, int64_t n, uint16_t *d_out, int64_t out_samples,
-                          uint32_t *d_skipped, unsigned flags, void *stream) {
-  if (!e) return fail("engine is NULL");
-  std::lock_guard<std::recursive_mutex> lk(e->mu);
-  if (!d_frames && !d_refs) return fail("bad prediction arguments: no frames");
-  if (predict_args_ok(e, nframes, d_items, n, d_out, out_samples, flags) != 0) return -1;
-  if ((reinterpret_cast<uintptr_t>(d_out) & 7) || (reinterpret_cast<uintptr_t>(d_items) & 7))
-    return fail("d_out and d_items must be 8-byte aligned");
-  if (n == 0) return 0;
-  HIP_TRY(hipSetDevice(e->device));
-  if (flush_open(e) != 0) return -1;  // (device-API work orders itself after the host calls)
-  if (ensure_pred_tables(e) != 0) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  const uint16_t *refs = d_refs ? d_refs : d_frames;
-  const bool engine_refs = !d_refs && e->opts.filter != MIP_FILTER_NONE;
-  if (engine_refs) {  // as mip_search_device: filter into the engine's reference scratch
-    if (nframes > e->opts.max_batch) return fail("nframes %d > max_batch %d", nframes, e->opts.max_batch);
-    if (e->refs_pending) HIP_TRY(hipStreamWaitEvent(s, e->refs_done, 0));
-    if (e->host_pending)
-      HIP_TRY(hipStreamWaitEvent(s, e->call_done[(e->host_calls - 1) % mip_engine::kCallRing], 0));
-    if (mip_filter_device(d_frames, e->d_refs, e->width, e->height, nframes, e->opts.filter, e->opts.kernel_idx, s) != 0)
-      return -1;
-    refs = e->d_refs;
-  }
-  if (predict_launch(e, refs, engine_refs, nframes, d_items, n, d_out, out_samples, d_skipped, flags, s) != 0) return -1;
-  if (engine_refs) {
-    HIP_TRY(hipEventRecord(e->refs_done, s));
-    e->refs_pending = true;
-  }
-  return 0;
-}
-
-int mip_predict_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
-                       const mip_pred_item *items, int64_t n, uint16_t *out, int64_t out_samples, int64_t *skipped) {
-  return mip_predict_frames_ex(e, frames, refs_or_null, nframes, items, n, out, out_samples, 0, skipped);
-}
-
-int mip_predict_frames_ex(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
-                          const mip_pred_item *items, int64_t n, uint16_t *out, int64_t out_samples, unsigned flags,
-                          int64_t *skipped) {
-  if (!e) return fail("engine is NULL");
-  std::lock_guard<std::recursive_mutex> lk(e->mu);
-  if (!frames && !refs_or_null) return fail("bad prediction arguments: no frames");
-  if (predict_args_ok(e, nframes, items, n, out, out_samples, flags) != 0) return -1;
-  if (out_samples && !out) return fail("bad prediction arguments: out is NULL");
-  // the list on the host: names outside the call's frames / the frame's CUs are the caller's bug
-  for (int64_t i = 0; i < n; i++) {
-    if (items[i].frame < 0 || items[i].frame >= nframes)
-      return fail("prediction item %lld: frame %d outside 0..%d", (long long)i, items[i].frame, nframes - 1);
-    if (items[i].cu < 0 || items[i].cu >= e->nctus * MIP_CUS_PER_CTU)
-      return fail("prediction item %lld: cu %d outside 0..%d", (long long)i, items[i].cu, e->nctus * MIP_CUS_PER_CTU - 1);
-  }
-  if (skipped) *skipped = 0;
-  if (out_samples == 0) {
-    if (skipped) *skipped = n;
-    return 0;
-  }
-  HIP_TRY(hipSetDevice(e->device));
-  if (quiesce(e) != 0) return -1;  // (host searches in flight use d_frames / d_refs)
-  if (ensure_pred_tables(e) != 0) return -1;
-  const size_t fs = (size_t)e->width * e->height, fbytes = fs * (size_t)nframes * 2;
-  const bool engine_refs = !refs_or_null && e->opts.filter != MIP_FILTER_NONE;
-  // the call's own device buffers (through the device block cache); the engine's frame buffers
-  // serve when the call's frames fit them
-  uint16_t *t_in = nullptr, *t_refs = nullptr, *d_out = nullptr;
-  mip_pred_item *d_items = nullptr;
-  uint32_t *d_skip = nullptr;
-  auto done = [&](int rc) {
-    for (void *p : {(void *)t_in, (void *)t_refs, (void *)d_out, (void *)d_items, (void *)d_skip}) dev_free(p);
-    return rc;
-  };
-#define PRED_TRY(expr)                                                                     \
-  do {                                                                                     \
-    hipError_t _e = (expr);                                                                \
-    if (_e != hipSuccess) return done(fail("%s: %s", #expr, hipGetErrorString(_e)));       \
-  } while (0)
-  uint16_t *d_in = e->d_frames, *d_refs = e->d_refs;
-  if (nframes > e->hp_frames) {
-    PRED_TRY(dev_malloc(e->device, (void **)&t_in, fbytes));
-    d_in = t_in;
-  }
-  if (engine_refs && (nframes > e->hp_frames || !d_refs)) {
-    PRED_TRY(dev_malloc(e->device, (void **)&t_refs, fbytes));
-    d_refs = t_refs;
-  }
-  PRED_TRY(dev_malloc(e->device, (void **)&d_out, (size_t)out_samples * 2));
-  PRED_TRY(dev_malloc(e->device, (void **)&d_items, std::max<size_t>(1, (size_t)n) * sizeof(mip_pred_item)));
-  PRED_TRY(dev_malloc(e->device, (void **)&d_skip, sizeof(uint32_t)));
-  hipStream_t s = e->stream;
-  PRED_TRY(hipMemcpyAsync(d_in, refs_or_null ? refs_or_null : frames, fbytes, hipMemcpyHostToDevice, s));
-  if (n) PRED_TRY(hipMemcpyAsync(d_items, items, (size_t)n * sizeof(mip_pred_item), hipMemcpyHostToDevice, s));
-  PRED_TRY(hipMemsetAsync(d_out, 0xff, (size_t)out_samples * 2, s));  // MIP_PRED_NONE
-  PRED_TRY(hipMemsetAsync(d_skip, 0, sizeof(uint32_t), s));
-  const uint16_t *refs = d_in;
-  if (engine_refs) {
-    // (in batches of max_batch frames like mip_filter_frames: the filter kernel's launch limit)
-    for (int f0 = 0; f0 < nframes; f0 += e->opts.max_batch) {
-      const int nb = std::min(e->opts.max_batch, nframes - f0);
-      if (mip_filter_device(d_in + f0 * fs, d_refs + f0 * fs, e->width, e->height, nb, e->opts.filter, e->opts.kernel_idx,
-                            s) != 0)
-        return done(-1);
-    }
-    refs = d_refs;
-  }
-  if (predict_launch(e, refs, engine_refs, nframes, d_items, n, d_out, out_samples, d_skip, flags, s) != 0) return done(-1);
-  uint32_t nskip = 0;
-  PRED_TRY(hipMemcpyAsync(out, d_out, (size_t)out_samples * 2, hipMemcpyDeviceToHost, s));
-  PRED_TRY(hipMemcpyAsync(&nskip, d_skip, sizeof nskip, hipMemcpyDeviceToHost, s));
-  PRED_TRY(hipStreamSynchronize(s));
-#undef PRED_TRY
-  e->refs_pending = false;
-  if (skipped) *skipped = nskip;
-  return done(0);
-}
-
-// ---------------------------------------------------------------- partition decision
-// The argument rules of both partition entry points (before any launch).
-static int partition_args_ok(int width, int height, int nframes, const int32_t *penalty, bool any_output) {
-  if (width <= 0 || height <= 0 || width % 4 || height % 4 || nframes < 1) return fail("bad partition arguments");
-  if (!any_output) return fail("partition: no output given");
-  if (!mipgpu::part_penalty_ok(penalty))
-    return fail("partition: a shape penalty is outside 0..%d", (int)mipgpu::kPartMaxPenalty);
-  if ((long long)nframes * mip_num_ctus(width, height) * MIP_CUS_PER_CTU > kMaxCus)
-    return fail("%d frames exceed %lld CUs per call", nframes, kMaxCus);
-  return 0;
-}
-
-int mip_partition_device(const int32_t *d_best_cost, const uint8_t *d_best_mode, int width, int height, int nframes,
-                         const int32_t *penalty, uint8_t *d_leaf, int32_t *d_ctu_cost, int32_t *d_ctu_leaves,
-                         mip_pred_item *d_items, void *stream) {
-  if (!d_best_cost) return fail("bad partition arguments: d_best_cost is NULL");
-  if (partition_args_ok(width, height, nframes, penalty, d_leaf || d_ctu_cost || d_ctu_leaves || d_items) != 0) return -1;
-  if (d_items && !d_best_mode) return fail("partition: d_items needs d_best_mode");
-  if (reinterpret_cast<uintptr_t>(d_items) & 7) return fail("partition: d_items must be 8-byte aligned");
-  mipgpu::PartitionArgs a{};
-  a.best_cost = d_best_cost;
-  a.best_mode = d_best_mode;
-  a.leaf = d_leaf;
-  a.ctu_cost = d_ctu_cost;
-  a.ctu_leaves = d_ctu_leaves;
-  a.items = d_items;
-  a.width = width;
-  a.height = height;
-  a.ctu_cols = (width + 127) / 128;
-  a.nctus = mip_num_ctus(width, height);
-  a.nframes = nframes;
-  for (int s = 0; s < MIP_NUM_SHAPES; s++) a.penalty.v[s] = penalty ? penalty[s] : 0;
-  HIP_TRY(mipgpu::launch_partition(a, (hipStream_t)stream));
-  return 0;
-}
-
-int mip_partition_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
-                         const int32_t *penalty, uint8_t *best_mode_out, int32_t *best_cost_out, uint8_t *leaf_out,
-                         int32_t *ctu_cost_out, int32_t *ctu_leaves_out) {
-  if (!e) return fail("engine is NULL");
-  std::lock_guard<std::recursive_mutex> lk(e->mu);
-  if (!frames) return fail("bad partition arguments: no frames");
-  if (partition_args_ok(e->width, e->height, nframes, penalty,
-                        best_mode_out || best_cost_out || leaf_out || ctu_cost_out || ctu_leaves_out) != 0)
-    return -1;
-  if (e->opts.best_k != 1) return fail("mip_partition_frames needs best_k <= 1 (got %d)", e->opts.best_k);
-  HIP_TRY(hipSetDevice(e->device));
-  if (quiesce(e) != 0) return -1;  // (host searches in flight use the engine buffers)
-  if (check_device_status(e) != 0) return -1;  // (an earlier device-API search's violation)
-  const size_t fs = (size_t)e->width * e->height, ncu = (size_t)e->nctus * MIP_CUS_PER_CTU, mb = (size_t)e->opts.max_batch;
-  // the partition outputs' device buffers, for max_batch frames: allocated at their first use,
-  // released with the engine
-  if (!e->d_part_leaf) HIP_TRY(dev_malloc(e->device, (void **)&e->d_part_leaf, mb * ncu));
-  if (!e->d_part_ctu) HIP_TRY(dev_malloc(e->device, (void **)&e->d_part_ctu, mb * e->nctus * 2 * sizeof(int32_t)));
-  uint16_t *t_refs = nullptr;  // caller references on an engine without a reference buffer
-  auto done = [&](int rc) {
-    dev_free(t_refs);
-    return rc;
-  };
-#define PART_TRY(expr)                                                                     \
-  do {                                                                                     \
-    hipError_t _e = (expr);                                                                \
-    if (_e != hipSuccess) return done(fail("%s: %s", #expr, hipGetErrorString(_e)));       \
-  } while (0)
-  uint16_t *d_refs = nullptr;
-  if (refs_or_null) {
-    d_refs = e->d_refs;
-    if (!d_refs) {
-      PART_TRY(dev_malloc(e->device, (void **)&t_refs, mb * fs * 2));
-      d_refs = t_refs;
-    }
-  }
-  hipStream_t s = e->stream;
-  int32_t *d_ctu_cost = e->d_part_ctu, *d_ctu_leaves = e->d_part_ctu + mb * e->nctus;
-  for (int f0 = 0; f0 < nframes; f0 += e->opts.max_batch) {
-    const size_t nb = (size_t)std::min(e->opts.max_batch, nframes - f0);
-    PART_TRY(hipMemcpyAsync(e->d_frames, frames + f0 * fs, nb * fs * 2, hipMemcpyHostToDevice, s));
-    if (d_refs) PART_TRY(hipMemcpyAsync(d_refs, refs_or_null + f0 * fs, nb * fs * 2, hipMemcpyHostToDevice, s));
-    // (without references the search filters the frames itself when the engine has a filter)
-    if (search_device_impl(e, e->d_frames, d_refs, (int)nb, nullptr, nullptr, nullptr, e->d_best, e->d_best_cost, s,
-                           d_refs != nullptr, device_status(e)) != 0)
-      return done(-1);
-    if (mip_partition_device(e->d_best_cost, e->d_best, e->width, e->height, (int)nb, penalty, e->d_part_leaf, d_ctu_cost,
-                             d_ctu_leaves, nullptr, s) != 0)
-      return done(-1);
-    if (best_mode_out) PART_TRY(hipMemcpyAsync(best_mode_out + f0 * ncu, e->d_best, nb * ncu, hipMemcpyDeviceToHost, s));
-    if (best_cost_out) PART_TRY(hipMemcpyAsync(best_cost_out + f0 * ncu, e->d_best_cost, nb * ncu * 4, hipMemcpyDeviceToHost, s));
-    if (leaf_out) PART_TRY(hipMemcpyAsync(leaf_out + f0 * ncu, e->d_part_leaf, nb * ncu, hipMemcpyDeviceToHost, s));
-    if (ctu_cost_out)
-      PART_TRY(hipMemcpyAsync(ctu_cost_out + (size_t)f0 * e->nctus, d_ctu_cost, nb * e->nctus * 4, hipMemcpyDeviceToHost, s));
-    if (ctu_leaves_out)
-      PART_TRY(hipMemcpyAsync(ctu_leaves_out + (size_t)f0 * e->nctus, d_ctu_leaves, nb * e->nctus * 4, hipMemcpyDeviceToHost, s));
-    PART_TRY(hipStreamSynchronize(s));
-  }
-#undef PART_TRY
-  e->refs_pending = false;
-  if (const uint32_t f = take_status(e, mip_engine::kCallRing)) return done(contract_error(f, "mip_partition_frames"));
-  return done(0);
-}
-
-// The whole device chain on host frames: decisions, Planar / DC merge, (angular merge,) partition
-// and the partition's predicted frames, chunk by chunk like mip_partition_frames.
-int mip_predicted_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
-                         const int32_t *penalty, const int32_t *bias, uint8_t *best_mode_out, int32_t *best_cost_out,
-                         uint8_t *leaf_out, int32_t *ctu_cost_out, int32_t *ctu_leaves_out, uint16_t *pred_out) {
-  return mip_predicted_frames_ex(e, frames, refs_or_null, nframes, penalty, bias, nullptr, 0, 0, 0, best_mode_out, best_cost_out,
-                                 leaf_out, ctu_cost_out, ctu_leaves_out, pred_out);
-}
-
-// With MIP_CHAIN_ANGULAR the angular merge runs between the Planar / DC merge and the partition,
-// and the prediction emits the angular leaves too.
-int mip_predicted_frames_ex(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
-                            const int32_t *penalty, const int32_t *bias, const uint8_t *ang_modes, int ang_nmodes,
-                            int32_t ang_bias, unsigned flags, uint8_t *best_mode_out, int32_t *best_cost_out, uint8_t *leaf_out,
-                            int32_t *ctu_cost_out, int32_t *ctu_leaves_out, uint16_t *pred_out) {
-  if (!e) return fail("engine is NULL");
-  std::lock_guard<std::recursive_mutex> lk(e->mu);
-  if (!frames) return fail("bad partition arguments: no frames");
-  if (partition_args_ok(e->width, e->height, nframes, penalty,
-                        best_mode_out || best_cost_out || leaf_out || ctu_cost_out || ctu_leaves_out || pred_out) != 0)
-    return -1;
-  if (!mipgpu::intra_bias_ok(bias)) return fail("intra: a bias is outside 0..%d", (int)mipgpu::kIntraMaxBias);
-  mipgpu::AngList ang_list_checked;  // (mip_angular_device checks the caller's list again, chunk by chunk)
-  switch (mipgpu::predicted_ex_args(flags, ang_modes, ang_nmodes, ang_bias, &ang_list_checked)) {
-    case mipgpu::kPredictedExOk: break;
-    case mipgpu::kPredictedExFlags: return fail("unknown chain flags 0x%x", flags);
-    case mipgpu::kPredictedExModes:
-      return fail("angular: modes must be 1..%d strictly increasing mode numbers in %d..%d (or NULL, 0 for all)", MIP_ANGULAR_MODES,
-                  MIP_ANGULAR_FIRST, MIP_ANGULAR_LAST);
-    case mipgpu::kPredictedExBias: return fail("angular: the bias is outside 0..%d", (int)mipgpu::kAngMaxBias);
-  }
-  const bool angular = (flags & MIP_CHAIN_ANGULAR) != 0;
-  if (e->opts.best_k != 1) return fail("mip_predicted_frames needs best_k <= 1 (got %d)", e->opts.best_k);
-  HIP_TRY(hipSetDevice(e->device));
-  if (quiesce(e) != 0) return -1;  // (host searches in flight use the engine buffers)
-  if (check_device_status(e) != 0) return -1;  // (an earlier device-API search's violation)
-  if (ensure_pred_tables(e) != 0) return -1;
-  const size_t fs = (size_t)e->width * e->height, ncu = (size_t)e->nctus * MIP_CUS_PER_CTU, mb = (size_t)e->opts.max_batch;
-  const size_t chunk = std::min(mb, (size_t)nframes), per_frame = (size_t)e->nctus * MIP_PART_MAX_LEAVES;  // list entries
-  if (!e->d_part_leaf) HIP_TRY(dev_malloc(e->device, (void **)&e->d_part_leaf, mb * ncu));
-  if (!e->d_part_ctu) HIP_TRY(dev_malloc(e->device, (void **)&e->d_part_ctu, mb * e->nctus * 2 * sizeof(int32_t)));
-  // the call's own device buffers (through the device block cache): caller references on an
-  // engine without a reference buffer, one chunk's item list and its frame canvases
-  uint16_t *t_refs = nullptr, *d_pred = nullptr;
-  mip_pred_item *d_items = nullptr;
-  auto done = [&](int rc) {
-    for (void *p : {(void *)t_refs, (void *)d_pred, (void *)d_items}) dev_free(p);
-    return rc;
-  };
-#define CHAIN_TRY(expr)                                                                    \
-  do {                                                                                     \
-    hipError_t _e = (expr);                                                                \
-    if (_e != hipSuccess) return done(fail("%s: %s", #expr, hipGetErrorString(_e)));       \
-  } while (0)
-  uint16_t *d_refs = nullptr;
-  if (refs_or_null) {
-    d_refs = e->d_refs;
-    if (!d_refs) {
-      CHAIN_TRY(dev_malloc(e->device, (void **)&t_refs, mb * fs * 2));
-      d_refs = t_refs;
-    }
-  }
-  if (pred_out) {
-    CHAIN_TRY(dev_malloc(e->device, (void **)&d_items, chunk * per_frame * sizeof(mip_pred_item)));
-    CHAIN_TRY(dev_malloc(e->device, (void **)&d_pred, chunk * fs * 2));
-  }
-  const bool engine_refs = !refs_or_null && e->opts.filter != MIP_FILTER_NONE;
-  hipStream_t s = e->stream;
-  int32_t *d_ctu_cost = e->d_part_ctu, *d_ctu_leaves = e->d_part_ctu + mb * e->nctus;
-  for (int f0 = 0; f0 < nframes; f0 += e->opts.max_batch) {
-    const size_t nb = (size_t)std::min(e->opts.max_batch, nframes - f0);
-    CHAIN_TRY(hipMemcpyAsync(e->d_frames, frames + f0 * fs, nb * fs * 2, hipMemcpyHostToDevice, s));
-    if (d_refs) CHAIN_TRY(hipMemcpyAsync(d_refs, refs_or_null + f0 * fs, nb * fs * 2, hipMemcpyHostToDevice, s));
-    // (without references the search filters the frames into e->d_refs when the engine has a
-    // filter; the merge and the prediction below read that buffer)
-    if (search_device_impl(e, e->d_frames, d_refs, (int)nb, nullptr, nullptr, nullptr, e->d_best, e->d_best_cost, s,
-                           d_refs != nullptr, device_status(e)) != 0)
-      return done(-1);
-    if (mip_intra_device(e, e->d_frames, d_refs, (int)nb, nullptr, nullptr, nullptr, bias, e->d_best, e->d_best_cost, s) != 0)
-      return done(-1);
-    if (angular && mip_angular_device(e, e->d_frames, d_refs, (int)nb, ang_modes, ang_nmodes, nullptr, nullptr, nullptr, nullptr,
-                                      nullptr, ang_bias, e->d_best, e->d_best_cost, s) != 0)
-      return done(-1);
-    // the list's frame indexes and offsets are the chunk's own: 0 .. nb-1 into d_pred
-    if (mip_partition_device(e->d_best_cost, e->d_best, e->width, e->height, (int)nb, penalty, e->d_part_leaf, d_ctu_cost,
-                             d_ctu_leaves, d_items, s) != 0)
-      return done(-1);
-    if (pred_out) {
-      CHAIN_TRY(hipMemsetAsync(d_pred, 0xff, nb * fs * 2, s));  // MIP_PRED_NONE
-      const uint16_t *refs = d_refs ? d_refs : engine_refs ? e->d_refs : e->d_frames;
-      if (predict_launch(e, refs, engine_refs, (int)nb, d_items, (int64_t)(nb * per_frame), d_pred, (int64_t)(nb * fs), nullptr,
-                         angular ? MIP_PRED_REGULAR | MIP_PRED_ANGULAR : MIP_PRED_REGULAR, s) != 0)
-        return done(-1);
-      CHAIN_TRY(hipMemcpyAsync(pred_out + f0 * fs, d_pred, nb * fs * 2, hipMemcpyDeviceToHost, s));
-    }
-    if (best_mode_out) CHAIN_TRY(hipMemcpyAsync(best_mode_out + f0 * ncu, e->d_best, nb * ncu, hipMemcpyDeviceToHost, s));
-    if (best_cost_out) CHAIN_TRY(hipMemcpyAsync(best_cost_out + f0 * ncu, e->d_best_cost, nb * ncu * 4, hipMemcpyDeviceToHost, s));
-    if (leaf_out) CHAIN_TRY(hipMemcpyAsync(leaf_out + f0 * ncu, e->d_part_leaf, nb * ncu, hipMemcpyDeviceToHost, s));
-    if (ctu_cost_out)
-      CHAIN_TRY(hipMemcpyAsync(ctu_cost_out + (size_t)f0 * e->nctus, d_ctu_cost, nb * e->nctus * 4, hipMemcpyDeviceToHost, s));
-    if (ctu_leaves_out)
-      CHAIN_TRY(hipMemcpyAsync(ctu_leaves_out + (size_t)f0 * e->nctus, d_ctu_leaves, nb * e->nctus * 4, hipMemcpyDeviceToHost, s));
-    CHAIN_TRY(hipStreamSynchronize(s));
-  }
-#undef CHAIN_TRY
-  e->refs_pending = false;
-  if (const uint32_t f = take_status(e, mip_engine::kCallRing)) return done(contract_error(f, "mip_predicted_frames"));
-  return done(0);
-}
-
-// ---------------------------------------------------------------- Planar / DC baseline costs
-// The engine's lane-slot table (mip_engine::d_intra_slots), uploaded once, and the prediction
-// tables' availability sets.
-static int ensure_intra_tables(mip_engine *e) {
-  if (ensure_pred_tables(e) != 0) return -1;
-  if (e->d_intra_slots) return 0;
-  int per_block = 0;
-  const std::vector<uint32_t> slots = mipgpu::intra_build_slots(&per_block);
-  if (slots.empty()) return fail("intra: the CU shapes do not fit the 32x32 blocks");
-  uint32_t *d = nullptr;
-  HIP_TRY(dev_malloc(e->device, (void **)&d, slots.size() * sizeof(uint32_t)));
-  if (hipMemcpy(d, slots.data(), slots.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
-    dev_free(d);
-    return fail("uploading the intra lane slots failed");
-  }
-  e->intra_slots_per_block = per_block;
-  e->d_intra_slots = d;  // (set last: the table is complete)
-  return 0;
-}
-
-// The argument rules of both intra entry points (before any launch).
-static int intra_args_ok(const mip_engine *e, int nframes, bool any_output) {
-  if (nframes < 1) return fail("bad intra arguments");
-  if (!any_output) return fail("intra: no output given");
-  if ((long long)nframes * e->nctus * MIP_CUS_PER_CTU > kMaxCus) return fail("%d frames exceed %lld CUs per call", nframes, kMaxCus);
-  return 0;
-}
-
-// The reference source of the regular-intra kernels (mip_intra_device, mip_angular_device): the
-// caller's references, the originals, or -- as mip_predict_device -- the engine's filter applied
-// into the engine's reference scratch, ordered after that scratch's previous reader.  The caller
-// records refs_done behind its kernel when *engine_refs is set (intra_reference_done).
-static int intra_reference_source(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes, hipStream_t s,
-                                  const uint16_t **refs, bool *engine_refs) {
-  *refs = d_refs ? d_refs : d_frames;
-  *engine_refs = !d_refs && e->opts.filter != MIP_FILTER_NONE;
-  if (*engine_refs) {
-    if (nframes > e->opts.max_batch) return fail("nframes %d > max_batch %d", nframes, e->opts.max_batch);
-    if (e->refs_pending) HIP_TRY(hipStreamWaitEvent(s, e->refs_done, 0));
-    if (e->host_pending)
-      HIP_TRY(hipStreamWaitEvent(s, e->call_done[(e->host_calls - 1) % mip_engine::kCallRing], 0));
-    if (mip_filter_device(d_frames, e->d_refs, e->width, e->height, nframes, e->opts.filter, e->opts.kernel_idx, s) != 0)
-      return -1;
-    *refs = e->d_refs;
-  }
-  return 0;
-}
-static int intra_reference_done(mip_engine *e, bool engine_refs, hipStream_t s) {
-  if (engine_refs) {
-    HIP_TRY(hipEventRecord(e->refs_done, s));
-    e->refs_pending = true;
-  }
-  return 0;
-}
-
-int mip_intra_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes, int32_t *d_cost,
-                     int32_t *d_sad, int32_t *d_satd, const int32_t *bias, uint8_t *d_best_mode, int32_t *d_best_cost,
-                     void *stream) {
-  if (!e) return fail("engine is NULL");
-  std::lock_guard<std::recursive_mutex> lk(e->mu);
-  if (!d_frames) return fail("bad intra arguments: no frames");
-  if (intra_args_ok(e, nframes, d_cost || d_sad || d_satd || d_best_mode || d_best_cost) != 0) return -1;
-  if (!d_best_mode != !d_best_cost) return fail("intra: d_best_mode and d_best_cost are given together");
-  if (!mipgpu::intra_bias_ok(bias)) return fail("intra: a bias is outside 0..%d", (int)mipgpu::kIntraMaxBias);
-  for (const void *p : {(const void *)d_cost, (const void *)d_sad, (const void *)d_satd})
-    if (reinterpret_cast<uintptr_t>(p) & 7) return fail("intra: the tables must be 8-byte aligned");
-  HIP_TRY(hipSetDevice(e->device));
-  if (flush_open(e) != 0) return -1;  // (device-API work orders itself after the host calls)
-  if (ensure_intra_tables(e) != 0) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  const uint16_t *refs = nullptr;
-  bool engine_refs = false;
-  if (intra_reference_source(e, d_frames, d_refs, nframes, s, &refs, &engine_refs) != 0) return -1;
-  mipgpu::IntraArgs a{};
-  a.orig = d_frames;
-  a.refs = refs;
-  a.unavail = e->d_pred_unavail[engine_refs ? 1 : 0];
-  a.slots = e->d_intra_slots;
-  a.slots_per_block = e->intra_slots_per_block;
-  a.cost = d_cost;
-  a.sad = d_sad;
-  a.satd = d_satd;
-  a.best_mode = d_best_mode;
-  a.best_cost = d_best_cost;
-  for (int k = 0; k < mipgpu::kIntraModes; k++) a.bias[k] = bias ? bias[k] : 0;
-  a.width = e->width;
-  a.height = e->height;
-  a.ctu_cols = e->ctu_cols;
-  a.nctus = e->nctus;
-  a.nframes = nframes;
-  HIP_TRY(mipgpu::launch_intra(a, s));
-  return intra_reference_done(e, engine_refs, s);
-}
-
-int mip_intra_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes, int32_t *cost_out,
-                     int32_t *sad_out, int32_t *satd_out) {
-  if (!e) return fail("engine is NULL");
-  std::lock_guard<std::recursive_mutex> lk(e->mu);
-  if (!frames) return fail("bad intra arguments: no frames");
-  if (intra_args_ok(e, nframes, cost_out || sad_out || satd_out) != 0) return -1;
-  HIP_TRY(hipSetDevice(e->device));
-  if (quiesce(e) != 0) return -1;  // (host searches in flight use the engine buffers)
-  const size_t fs = (size_t)e->width * e->height, mb = (size_t)e->opts.max_batch;
-  const size_t entries = (size_t)e->nctus * MIP_CUS_PER_CTU * mipgpu::kIntraModes;  // per frame and table
-  // the call's own device buffers (through the device block cache): caller references on an
-  // engine without a reference buffer, and one table of max_batch frames per output asked for
-  int32_t *const host_out[3] = {cost_out, sad_out, satd_out};
-  uint16_t *t_refs = nullptr;
-  int32_t *d_out[3] = {nullptr, nullptr, nullptr};
-  auto done = [&](int rc) {
-    for (void *p : {(void *)t_refs, (void *)d_out[0], (void *)d_out[1], (void *)d_out[2]}) dev_free(p);
-    return rc;
-  };
-#define INTRA_TRY(expr)                                                                    \
-  do {                                                                                     \
-    hipError_t _e = (expr);                                                                \
-    if (_e != hipSuccess) return done(fail("%s: %s", #expr, hipGetErrorString(_e)));       \
-  } while (0)
-  uint16_t *d_refs = nullptr;
-  if (refs_or_null) {
-    d_refs = e->d_refs;
-    if (!d_refs) {
-      INTRA_TRY(dev_malloc(e->device, (void **)&t_refs, mb * fs * 2));
-      d_refs = t_refs;
-    }
-  }
-  const size_t chunk = std::min(mb, (size_t)nframes);
-  for (int t = 0; t < 3; t++)
-    if (host_out[t]) INTRA_TRY(dev_malloc(e->device, (void **)&d_out[t], chunk * entries * sizeof(int32_t)));
-  hipStream_t s = e->stream;
-  for (int f0 = 0; f0 < nframes; f0 += e->opts.max_batch) {
-    const size_t nb = (size_t)std::min(e->opts.max_batch, nframes - f0);
-    INTRA_TRY(hipMemcpyAsync(e->d_frames, frames + f0 * fs, nb * fs * 2, hipMemcpyHostToDevice, s));
-    if (d_refs) INTRA_TRY(hipMemcpyAsync(d_refs, refs_or_null + f0 * fs, nb * fs * 2, hipMemcpyHostToDevice, s));
-    // (without references the device entry point filters the frames itself when the engine has a filter)
-    if (mip_intra_device(e, e->d_frames, d_refs, (int)nb, d_out[0], d_out[1], d_out[2], nullptr, nullptr, nullptr, s) != 0)
-      return done(-1);
-    for (int t = 0; t < 3; t++)
-      if (host_out[t])
-        INTRA_TRY(hipMemcpyAsync(host_out[t] + f0 * entries, d_out[t], nb * entries * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    INTRA_TRY(hipStreamSynchronize(s));
-  }
-#undef INTRA_TRY
-  e->refs_pending = false;
-  return done(0);
-}
-
-// ---------------------------------------------------------------- angular intra costs
-// The argument rules of both angular entry points (before any launch).
-static int angular_args_ok(const mip_engine *e, int nframes, const uint8_t *modes, int nmodes, bool any_output,
-                           mipgpu::AngList *list) {
-  if (intra_args_ok(e, nframes, any_output) != 0) return -1;
-  if (!mipgpu::ang_list(modes, nmodes, list))
-    return fail("angular: modes must be 1..%d strictly increasing mode numbers in %d..%d (or NULL, 0 for all)", MIP_ANGULAR_MODES,
-                MIP_ANGULAR_FIRST, MIP_ANGULAR_LAST);
-  return 0;
-}
-
-// Both device entry points: refine == false is mip_angular_device (seeds and d_tried not looked
-// at), refine == true mip_angular_refine_device.
-static int angular_device_impl(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes, const uint8_t *modes,
-                               int nmodes, bool refine, int seeds, int32_t *d_cost, int32_t *d_sad, int32_t *d_satd,
-                               uint8_t *d_ang_mode, int32_t *d_ang_cost, uint8_t *d_tried, int32_t bias, uint8_t *d_best_mode,
-                               int32_t *d_best_cost, void *stream) {
-  if (!e) return fail("engine is NULL");
-  std::lock_guard<std::recursive_mutex> lk(e->mu);
-  if (!d_frames) return fail("bad angular arguments: no frames");
-  mipgpu::AngList list;
-  if (angular_args_ok(e, nframes, modes, nmodes,
-                      d_cost || d_sad || d_satd || d_ang_mode || d_ang_cost || d_best_mode || d_best_cost || (refine && d_tried),
-                      &list) != 0)
-    return -1;
-  if (refine && !mipgpu::ang_seeds_ok(seeds)) return fail("angular: seeds must be 1..%d", MIP_ANGULAR_MAX_SEEDS);
-  if (!d_ang_mode != !d_ang_cost) return fail("angular: d_ang_mode and d_ang_cost are given together");
-  if (!d_best_mode != !d_best_cost) return fail("angular: d_best_mode and d_best_cost are given together");
-  if (!mipgpu::ang_bias_ok(bias)) return fail("angular: the bias is outside 0..%d", (int)mipgpu::kAngMaxBias);
-  for (const void *p : {(const void *)d_cost, (const void *)d_sad, (const void *)d_satd, (const void *)d_ang_cost, (const void *)d_best_cost})
-    if (reinterpret_cast<uintptr_t>(p) & 3) return fail("angular: int32 outputs must be 4-byte aligned");
-  HIP_TRY(hipSetDevice(e->device));
-  if (flush_open(e) != 0) return -1;  // (device-API work orders itself after the host calls)
-  if (ensure_intra_tables(e) != 0) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  const uint16_t *refs = nullptr;
-  bool engine_refs = false;
-  if (intra_reference_source(e, d_frames, d_refs, nframes, s, &refs, &engine_refs) != 0) return -1;
-  mipgpu::AngularRefineArgs a{};  // (the plain launch takes its AngularArgs part)
-  a.orig = d_frames;
-  a.refs = refs;
-  a.unavail = e->d_pred_unavail[engine_refs ? 1 : 0];
-  a.slots = e->d_intra_slots;
-  a.slots_per_block = e->intra_slots_per_block;
-  a.cost = d_cost;
-  a.sad = d_sad;
-  a.satd = d_satd;
-  a.ang_mode = d_ang_mode;
-  a.ang_cost = d_ang_cost;
-  a.best_mode = d_best_mode;
-  a.best_cost = d_best_cost;
-  a.bias = bias;
-  a.width = e->width;
-  a.height = e->height;
-  a.ctu_cols = e->ctu_cols;
-  a.nctus = e->nctus;
-  a.nframes = nframes;
-  a.nmodes = list.n;
-  for (int k = 0; k < 3; k++) a.listed[k] = list.listed[k];
-  for (int q = 0; q < list.n; q++) a.modes[q] = list.packed[q];
-  if (refine) {
-    a.tried = d_tried;
-    a.nseeds = std::min(seeds, list.n);
-    for (int m = MIP_ANGULAR_FIRST; m <= MIP_ANGULAR_LAST; m++) a.all[m - MIP_ANGULAR_FIRST] = mipgpu::ang_pack(m);
-    HIP_TRY(mipgpu::launch_angular_refine(a, s));
-  } else {
-    HIP_TRY(mipgpu::launch_angular(a, s));
-  }
-  return intra_reference_done(e, engine_refs, s);
-}
-
-int mip_angular_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes, const uint8_t *modes,
-                       int nmodes, int32_t *d_cost, int32_t *d_sad, int32_t *d_satd, uint8_t *d_ang_mode, int32_t *d_ang_cost,
-                       int32_t bias, uint8_t *d_best_mode, int32_t *d_best_cost, void *stream) {
-  return angular_device_impl(e, d_frames, d_refs, nframes, modes, nmodes, false, 0, d_cost, d_sad, d_satd, d_ang_mode, d_ang_cost,
-                             nullptr, bias, d_best_mode, d_best_cost, stream);
-}
-
-int mip_angular_refine_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes, const uint8_t *modes,
-                              int nmodes, int seeds, int32_t *d_cost, int32_t *d_sad, int32_t *d_satd, uint8_t *d_ang_mode,
-                              int32_t *d_ang_cost, uint8_t *d_ang_tried, int32_t bias, uint8_t *d_best_mode, int32_t *d_best_cost,
-                              void *stream) {
-  return angular_device_impl(e, d_frames, d_refs, nframes, modes, nmodes, true, seeds, d_cost, d_sad, d_satd, d_ang_mode, d_ang_cost,
-                             d_ang_tried, bias, d_best_mode, d_best_cost, stream);
-}
-
-// With cost_out the chunk is cut so that the call's device table stays within this bound (one
-// frame at least): a 1080p frame's table is 189 MB.
-static constexpr size_t kAngularTableBytes = (size_t)256 << 20;
-
-// Both host calls (refine as in angular_device_impl).
-static int angular_frames_impl(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes, const uint8_t *modes,
-                               int nmodes, bool refine, int seeds, int32_t *cost_out, uint8_t *ang_mode_out, int32_t *ang_cost_out,
-                               uint8_t *tried_out) {
-  if (!e) return fail("engine is NULL");
-  std::lock_guard<std::recursive_mutex> lk(e->mu);
-  if (!frames) return fail("bad angular arguments: no frames");
-  mipgpu::AngList list;
-  if (angular_args_ok(e, nframes, modes, nmodes, cost_out || ang_mode_out || ang_cost_out || (refine && tried_out), &list) != 0) return -1;
-  if (!ang_mode_out != !ang_cost_out) return fail("angular: ang_mode_out and ang_cost_out are given together");
-  if (refine && !mipgpu::ang_seeds_ok(seeds)) return fail("angular: seeds must be 1..%d", MIP_ANGULAR_MAX_SEEDS);
-  if (!refine) tried_out = nullptr;
-  HIP_TRY(hipSetDevice(e->device));
-  if (quiesce(e) != 0) return -1;  // (host searches in flight use the engine buffers)
-  const size_t fs = (size_t)e->width * e->height, mb = (size_t)e->opts.max_batch, ncu = (size_t)e->nctus * MIP_CUS_PER_CTU;
-  const size_t entries = ncu * mipgpu::kAngModes;  // per frame of the table
-  size_t chunk = std::min(mb, (size_t)nframes);
-  if (cost_out) chunk = std::max<size_t>(1, std::min(chunk, kAngularTableBytes / (entries * sizeof(int32_t))));
-  // the call's own device buffers (through the device block cache)
-  uint16_t *t_refs = nullptr;
-  int32_t *d_cost = nullptr, *d_ang_cost = nullptr;
-  uint8_t *d_ang_mode = nullptr, *d_tried = nullptr;
-  auto done = [&](int rc) {
-    for (void *p : {(void *)t_refs, (void *)d_cost, (void *)d_ang_cost, (void *)d_ang_mode, (void *)d_tried}) dev_free(p);
-    return rc;
-  };
-#define ANG_TRY(expr)                                                                      \
-  do {                                                                                     \
-    hipError_t _e = (expr);                                                                \
-    if (_e != hipSuccess) return done(fail("%s: %s", #expr, hipGetErrorString(_e)));       \
-  } while (0)
-  uint16_t *d_refs = nullptr;
-  if (refs_or_null) {
-    d_refs = e->d_refs;
-    if (!d_refs) {
-      ANG_TRY(dev_malloc(e->device, (void **)&t_refs, chunk * fs * 2));
-      d_refs = t_refs;
-    }
-  }
-  if (cost_out) ANG_TRY(dev_malloc(e->device, (void **)&d_cost, chunk * entries * sizeof(int32_t)));
-  if (ang_cost_out) {
-    ANG_TRY(dev_malloc(e->device, (void **)&d_ang_cost, chunk * ncu * sizeof(int32_t)));
-    ANG_TRY(dev_malloc(e->device, (void **)&d_ang_mode, chunk * ncu));
-  }
-  if (tried_out) ANG_TRY(dev_malloc(e->device, (void **)&d_tried, chunk * ncu));
-  hipStream_t s = e->stream;
-  for (size_t f0 = 0; f0 < (size_t)nframes; f0 += chunk) {
-    const size_t nb = std::min(chunk, (size_t)nframes - f0);
-    ANG_TRY(hipMemcpyAsync(e->d_frames, frames + f0 * fs, nb * fs * 2, hipMemcpyHostToDevice, s));
-    if (d_refs) ANG_TRY(hipMemcpyAsync(d_refs, refs_or_null + f0 * fs, nb * fs * 2, hipMemcpyHostToDevice, s));
-    // (without references the device entry point filters the frames itself when the engine has a filter)
-    if (angular_device_impl(e, e->d_frames, d_refs, (int)nb, modes, nmodes, refine, seeds, d_cost, nullptr, nullptr, d_ang_mode,
-                            d_ang_cost, d_tried, 0, nullptr, nullptr, s) != 0)
-      return done(-1);
-    if (tried_out) ANG_TRY(hipMemcpyAsync(tried_out + f0 * ncu, d_tried, nb * ncu, hipMemcpyDeviceToHost, s));
-    if (cost_out) ANG_TRY(hipMemcpyAsync(cost_out + f0 * entries, d_cost, nb * entries * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (ang_cost_out) {
-      ANG_TRY(hipMemcpyAsync(ang_cost_out + f0 * ncu, d_ang_cost, nb * ncu * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-      ANG_TRY(hipMemcpyAsync(ang_mode_out + f0 * ncu, d_ang_mode, nb * ncu, hipMemcpyDeviceToHost, s));
-    }
-    ANG_TRY(hipStreamSynchronize(s));
-  }
-#undef ANG_TRY
-  e->refs_pending = false;
-  return done(0);
-}
-
-int mip_angular_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes, const uint8_t *modes,
-                       int nmodes, int32_t *cost_out, uint8_t *ang_mode_out, int32_t *ang_cost_out) {
-  return angular_frames_impl(e, frames, refs_or_null, nframes, modes, nmodes, false, 0, cost_out, ang_mode_out, ang_cost_out, nullptr);
-}
-
-int mip_angular_refine_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes, const uint8_t *modes,
-                              int nmodes, int seeds, int32_t *cost_out, uint8_t *ang_mode_out, int32_t *ang_cost_out,
-                              uint8_t *tried_out) {
-  return angular_frames_impl(e, frames, refs_or_null, nframes, modes, nmodes, true, seeds, cost_out, ang_mode_out, ang_cost_out,
-                             tried_out);
 }
 
 double mip_time_search_device(mip_engine *e, const uint16_t *d_frames, const uint16_t *d_refs, int nframes,
