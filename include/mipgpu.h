@@ -637,6 +637,84 @@ int mip_predicted_frames_ex(mip_engine *e, const uint16_t *frames, const uint16_
                             uint8_t *best_mode_out, int32_t *best_cost_out, uint8_t *leaf_out,
                             int32_t *ctu_cost_out, int32_t *ctu_leaves_out, uint16_t *pred_out);
 
+/* K-best candidate lists over every mode family (additive to ABI 7; no reference counterpart):
+ * for every CU the k lowest-cost modes among its MIP modes, Planar, DC and the angular modes, in
+ * one list -- what an encoder's rough mode decision hands to full RD (VTM takes two or three per
+ * block, MIP and regular modes together).  mip_candidates_device merges the families' per-CU
+ * costs, which the other entry points leave in device memory; no table goes to the host.  No
+ * engine is needed.  Asynchronous on `stream`.  Argument errors are reported before any launch
+ * and nothing is written.
+ *
+ * CUs are indexed as in best_mode_out: [nframes][nCTUs*5380].  Each family is optional (a NULL
+ * pointer: not given), at least one must be given.
+ *
+ * MIP.  d_mip_mode / d_mip_cost (given together): uint8 / int32 [nframes][nCTUs*5380][kin], kin in
+ *   1..32 (kin is not looked at without them) -- the decision lists of mip_search_device on an
+ *   engine with best_k = kin, or of mip_topk_device.  Entry r of a CU is a candidate iff
+ *   mode <= 31 and cost != MIP_COST_UNAVAILABLE; its code is the mode, its value the cost.  Any
+ *   other entry (0xff, a mode above 31, MIP_COST_UNAVAILABLE) is simply absent.  The list is
+ *   data: no entry ever moves an address.
+ * Planar / DC.  d_intra_cost: int32 [nframes][nCTUs*5380][2], the d_cost table of
+ *   mip_intra_device.  A slot that is not MIP_COST_UNAVAILABLE is a candidate; its code is
+ *   MIP_MODE_PLANAR (slot 0) / MIP_MODE_DC (slot 1), its value cost + intra_bias[slot].
+ *   intra_bias is a HOST array of two int32 in 0 .. 1<<20, NULL = zeros (checked only with
+ *   d_intra_cost).
+ * Angular.  d_ang_cost: int32 [nframes][nCTUs*5380][65], the d_cost table of mip_angular_device
+ *   or mip_angular_refine_device.  Every slot that is not MIP_COST_UNAVAILABLE is a candidate;
+ *   its code is MIP_MODE_ANGULAR(slot + 2), its value cost + ang_bias, ang_bias in 0 .. 1<<20
+ *   (checked only with d_ang_cost).  Slots of modes that were not listed or not evaluated drop
+ *   out by themselves: a refined table contributes exactly the CU's set E.
+ * int32 arrays need 4-byte alignment only.
+ *
+ * Order.  The candidates of a CU are sorted by (value, rank), lowest first.  The rank of MIP mode
+ * v is v (0..31), of Planar 32, of DC 33, of angular mode m 32 + m (34..98).  This is the order
+ * of the existing merges -- MIP, Planar, DC, angular; the lower mode first inside a family; a
+ * later candidate wins only if strictly cheaper -- so with the same biases entry 0 is, bit for
+ * bit, the decision that the search's argmin, mip_intra_device's merge and
+ * mip_angular_device's / mip_angular_refine_device's merge leave.
+ *
+ * Outputs.  d_modes uint8 and d_costs int32, [nframes][nCTUs*5380][k], k in 1..MIP_CAND_MAX_K;
+ * either may be NULL, not both.  No output may overlap an input or the other output (an error
+ * before any launch).  The first min(k, number of candidates) entries of a CU are the sorted
+ * candidates' codes and values (biased, as the merges write them); every later entry is 0xff /
+ * MIP_COST_UNAVAILABLE.  Every entry of a given output is written.  A CU without a candidate is
+ * 0xff / MIP_COST_UNAVAILABLE throughout (an unavailable CU is MIP_COST_UNAVAILABLE in every
+ * family).
+ *
+ * Domain.  Costs the engine produces are at most 2*64*64*1023 = 8 380 416, so cost plus bias stays
+ * below 1<<24.  A table or list value other than MIP_COST_UNAVAILABLE outside
+ * 0 .. (1<<24) - 1 - (1<<20), or a MIP list that names a mode twice, gives an unspecified result:
+ * memory-safe (every code written is still one of the 99 codes or 0xff) and deterministic. */
+#define MIP_CAND_MAX_K 32
+int mip_candidates_device(int width, int height, int nframes, int k,
+                          const uint8_t *d_mip_mode, const int32_t *d_mip_cost, int kin,
+                          const int32_t *d_intra_cost, const int32_t *intra_bias,
+                          const int32_t *d_ang_cost, int32_t ang_bias,
+                          uint8_t *d_modes, int32_t *d_costs, void *stream);
+
+/* The candidate lists of host frames, synchronous like mip_partition_frames (it first waits for
+ * every call in flight; an open merged chunk is launched).  Per chunk: upload; filter, if the
+ * engine has one and no references are given; the search, with MIP lists of length min(k, 32)
+ * whatever opts.best_k is; with MIP_CAND_REGULAR the Planar / DC table of mip_intra_device; with
+ * MIP_CAND_ANGULAR the angular table over the list ang_modes / ang_nmodes (mip_angular_device's
+ * rules: NULL with 0 = all 65) -- ang_seeds == 0 runs mip_angular_device, 1 ..
+ * MIP_ANGULAR_MAX_SEEDS mip_angular_refine_device with that many seeds; then
+ * mip_candidates_device over the families that ran, with intra_bias (NULL = zeros) and ang_bias;
+ * download.  flags == 0 gives the MIP lists alone.  Without MIP_CAND_ANGULAR the angular
+ * arguments are not looked at, without MIP_CAND_REGULAR intra_bias is not.  Any other flag bit, a
+ * bad list, bias, seeds or k is an error before any launch.
+ * modes_out uint8 / costs_out int32: [nframes][nCTUs*5380][k], either may be NULL, not both.
+ * Chunks hold at most max_batch frames and are cut further, as in mip_angular_frames, so that the
+ * chunk's device tables -- the MIP cost table (the search writes one unless k == 1 on an engine
+ * with best_k <= 1), the Planar / DC table, the angular table -- stay within 256 MiB together,
+ * always at least one frame.  Results do not depend on the chunking. */
+#define MIP_CAND_REGULAR 1u   /* flags bit: Planar and DC are candidates */
+#define MIP_CAND_ANGULAR 2u   /* flags bit: the angular modes of the list are candidates */
+int mip_candidates_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
+                          int k, unsigned flags, const int32_t *intra_bias,
+                          const uint8_t *ang_modes, int ang_nmodes, int ang_seeds, int32_t ang_bias,
+                          uint8_t *modes_out, int32_t *costs_out);
+
 /* Streaming device-to-device copy of `bytes` (a multiple of 16, 16-byte aligned pointers),
  * asynchronous on `stream`: 16 bytes per lane, four loads in flight per lane -- the HBM copy
  * rate bench.py prices the filter kernel against (no reference counterpart). */

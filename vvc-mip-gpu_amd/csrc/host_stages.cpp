@@ -1,12 +1,13 @@
 // host_stages.cpp -- the stages behind the search (include/mipgpu.h): prediction output, the
-// partition decision, the Planar / DC and angular intra costs and the chains of them.  Each has a
-// device entry point (the caller's buffers and stream) and a host wrapper that walks the call's
-// frames through the engine buffers in chunks (walk_chunks).
+// partition decision, the Planar / DC and angular intra costs, the candidate lists and the chains
+// of them.  Each has a device entry point (the caller's buffers and stream) and a host wrapper that
+// walks the call's frames through the engine buffers in chunks (walk_chunks).
 #include "engine.h"
 
 #include <algorithm>
 
 #include "angular_plan.h"
+#include "candidates_plan.h"
 #include "intra_plan.h"
 #include "partition_plan.h"
 #include "predict_rule.h"
@@ -607,6 +608,95 @@ int mip_angular_refine_frames(mip_engine *e, const uint16_t *frames, const uint1
                               uint8_t *tried_out) {
   return angular_frames_impl(e, frames, refs_or_null, nframes, modes, nmodes, true, seeds, cost_out, ang_mode_out, ang_cost_out,
                              tried_out);
+}
+
+// ---------------------------------------------------------------- K-best candidate lists
+int mip_candidates_device(int width, int height, int nframes, int k, const uint8_t *d_mip_mode, const int32_t *d_mip_cost, int kin,
+                          const int32_t *d_intra_cost, const int32_t *intra_bias, const int32_t *d_ang_cost, int32_t ang_bias,
+                          uint8_t *d_modes, int32_t *d_costs, void *stream) {
+  const mipgpu::CandArgs rule = mipgpu::cand_args(width, height, nframes, k, d_mip_mode, d_mip_cost, kin, d_intra_cost, intra_bias,
+                                                  d_ang_cost, ang_bias, d_modes, d_costs);
+  if (rule != mipgpu::kCandOk) return fail("%s", mipgpu::cand_args_text(rule));
+  mipgpu::CandidatesArgs a{};
+  a.mip_mode = d_mip_mode;
+  a.mip_cost = d_mip_cost;
+  a.kin = d_mip_mode ? kin : 0;
+  a.intra_cost = d_intra_cost;
+  for (int s = 0; s < mipgpu::kIntraModes; s++) a.intra_bias[s] = d_intra_cost && intra_bias ? intra_bias[s] : 0;
+  a.ang_cost = d_ang_cost;
+  a.ang_bias = d_ang_cost ? ang_bias : 0;
+  a.modes = d_modes;
+  a.costs = d_costs;
+  a.total_cus = mipgpu::cand_cus(width, height, nframes);
+  a.k = k;
+  HIP_TRY(mipgpu::launch_candidates(a, (hipStream_t)stream));
+  return 0;
+}
+
+int mip_candidates_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes, int k, unsigned flags,
+                          const int32_t *intra_bias, const uint8_t *ang_modes, int ang_nmodes, int ang_seeds, int32_t ang_bias,
+                          uint8_t *modes_out, int32_t *costs_out) {
+  if (!e) return fail("engine is NULL");
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  if (!frames) return fail("bad candidates arguments: no frames");
+  if (intra_args_ok(e, nframes, modes_out || costs_out) != 0) return -1;
+  switch (mipgpu::cand_chain_args(flags, k, intra_bias, ang_modes, ang_nmodes, ang_seeds, ang_bias)) {
+    case mipgpu::kCandChainOk: break;
+    case mipgpu::kCandChainFlags: return fail("unknown candidates flags 0x%x", flags);
+    case mipgpu::kCandChainK: return fail("%s", mipgpu::cand_args_text(mipgpu::kCandK));
+    case mipgpu::kCandChainIntraBias: return fail("%s", mipgpu::cand_args_text(mipgpu::kCandIntraBias));
+    case mipgpu::kCandChainModes:
+      return fail("angular: modes must be 1..%d strictly increasing mode numbers in %d..%d (or NULL, 0 for all)", MIP_ANGULAR_MODES,
+                  MIP_ANGULAR_FIRST, MIP_ANGULAR_LAST);
+    case mipgpu::kCandChainSeeds: return fail("angular: seeds must be 0..%d", MIP_ANGULAR_MAX_SEEDS);
+    case mipgpu::kCandChainAngBias: return fail("%s", mipgpu::cand_args_text(mipgpu::kCandAngBias));
+  }
+  const bool regular = (flags & MIP_CAND_REGULAR) != 0, angular = (flags & MIP_CAND_ANGULAR) != 0;
+  HIP_TRY(hipSetDevice(e->device));
+  if (quiesce(e) != 0) return -1;  // (host searches in flight use the engine buffers)
+  if (check_device_status(e) != 0) return -1;  // (an earlier device-API search's violation)
+  // the MIP lists: the search's own decisions when one entry is asked for and the engine keeps
+  // argmins (best_k 1), else a cost table and the decision lists of length kin from it
+  const int kin = std::min(k, mipgpu::kCandMaxKin);
+  const bool mip_table = !(kin == 1 && e->opts.best_k == 1);
+  const size_t ncu = (size_t)e->nctus * MIP_CUS_PER_CTU;
+  const size_t mip_bytes = mip_table ? (size_t)e->nctus * MIP_COSTS_PER_CTU_ABI * sizeof(int32_t) : 0;  // per frame
+  const size_t intra_bytes = regular ? ncu * mipgpu::kIntraModes * sizeof(int32_t) : 0;
+  const size_t ang_bytes = angular ? ncu * mipgpu::kAngModes * sizeof(int32_t) : 0;
+  const int chunk = mipgpu::stage_chunk_frames(e->opts.max_batch, nframes, mip_bytes + intra_bytes + ang_bytes);
+  // the call's own device buffers (through the device block cache)
+  DevScratch scratch(e->device);
+  int32_t *d_table = nullptr, *d_intra = nullptr, *d_ang = nullptr, *d_mip_cost = nullptr, *d_costs = nullptr;
+  uint8_t *d_mip_mode = nullptr, *d_modes = nullptr;
+  if (mip_table) HIP_TRY(scratch.take(d_table, chunk * mip_bytes));
+  if (regular) HIP_TRY(scratch.take(d_intra, chunk * intra_bytes));
+  if (angular) HIP_TRY(scratch.take(d_ang, chunk * ang_bytes));
+  HIP_TRY(scratch.take(d_mip_cost, chunk * ncu * kin * sizeof(int32_t)));
+  HIP_TRY(scratch.take(d_mip_mode, chunk * ncu * kin));
+  if (costs_out) HIP_TRY(scratch.take(d_costs, chunk * ncu * k * sizeof(int32_t)));
+  if (modes_out) HIP_TRY(scratch.take(d_modes, chunk * ncu * k));
+  hipStream_t s = e->stream;
+  auto stages = [&](int nb, const uint16_t *d_refs) {
+    // (without references every stage filters the frames into e->d_refs itself when the engine has a filter)
+    if (search_device_impl(e, e->d_frames, d_refs, nb, d_table, nullptr, nullptr, mip_table ? nullptr : d_mip_mode,
+                           mip_table ? nullptr : d_mip_cost, s, d_refs != nullptr, device_status(e)) != 0)
+      return -1;
+    if (mip_table) {
+      const mipgpu::BestArgs b{d_table, d_mip_mode, d_mip_cost, (int)(nb * ncu), kin};
+      HIP_TRY(mipgpu::launch_best_modes(b, s));
+    }
+    if (regular && mip_intra_device(e, e->d_frames, d_refs, nb, d_intra, nullptr, nullptr, nullptr, nullptr, nullptr, s) != 0) return -1;
+    if (angular && angular_device_impl(e, e->d_frames, d_refs, nb, ang_modes, ang_nmodes, ang_seeds != 0, ang_seeds, d_ang, nullptr,
+                                       nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, s) != 0)
+      return -1;
+    return mip_candidates_device(e->width, e->height, nb, k, d_mip_mode, d_mip_cost, kin, d_intra, intra_bias, d_ang, ang_bias, d_modes,
+                                 d_costs, s);
+  };
+  if (walk_chunks(e, frames, refs_or_null, nframes, chunk, {{modes_out, d_modes, ncu * k}, {costs_out, d_costs, ncu * k * sizeof(int32_t)}},
+                  stages) != 0)
+    return -1;
+  if (const uint32_t f = take_status(e, mip_engine::kCallRing)) return contract_error(f, "mip_candidates_frames");
+  return 0;
 }
 
 }  // extern "C"

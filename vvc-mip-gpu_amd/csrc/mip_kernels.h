@@ -1,7 +1,7 @@
 // mip_kernels.h -- launch interface between the C-ABI host code (mipgpu.cpp, host_pipeline.cpp)
 // and the gfx950 kernels (mip_search.hip, mip_decide.hip, mip_filter.hip, mip_fixup.hip,
 // mip_predict.hip, mip_predict_angular.hip, mip_partition.hip, mip_intra.hip, mip_angular.hip,
-// mip_angular_refine.hip).  Not part of the public ABI.
+// mip_angular_refine.hip, mip_candidates.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -249,5 +249,22 @@ struct AngularRefineArgs : AngularArgs {
   uint32_t all[65];           // ang_pack of every mode 2..66 (staged in LDS: a per-lane lookup)
 };
 hipError_t launch_angular_refine(const AngularRefineArgs &a, hipStream_t s);
+
+// K-best candidate lists over the mode families (candidates_kernel, mip_candidates.hip): one lane
+// per CU, one wave per workgroup, the CU's keys (candidates_plan.h) in one LDS row.
+struct CandidatesArgs {
+  const uint8_t *mip_mode;    // optional family, both or neither: [total_cus][kin]
+  const int32_t *mip_cost;
+  int kin;                    // 1..32 with a MIP list
+  const int32_t *intra_cost;  // optional family: [total_cus][2]
+  int32_t intra_bias[2];      // 0 .. 1 << 20 (checked by the caller)
+  const int32_t *ang_cost;    // optional family: [total_cus][65]
+  int32_t ang_bias;
+  uint8_t *modes;             // outputs, at least one: [total_cus][k]
+  int32_t *costs;
+  long long total_cus;        // frames * nctus * 5380, <= 2^31 - 256
+  int k;                      // 1..32
+};
+hipError_t launch_candidates(const CandidatesArgs &a, hipStream_t s);
 
 }  // namespace mipgpu

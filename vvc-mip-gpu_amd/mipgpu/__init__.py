@@ -71,6 +71,9 @@ ANGULAR_EVEN_MODES = tuple(range(2, 67, 2))   # the 33 even modes: the usual coa
 PRED_REGULAR = 1                           # MIP_PRED_REGULAR: flags bit of predict(..., regular=True)
 PRED_ANGULAR = 4                           # MIP_PRED_ANGULAR: flags bit of predict(..., angular=True)
 CHAIN_ANGULAR = 1                          # MIP_CHAIN_ANGULAR: flags bit of mip_predicted_frames_ex (the angular stage)
+CAND_REGULAR = 1                           # MIP_CAND_REGULAR: flags bit of mip_candidates_frames (Planar / DC are candidates)
+CAND_ANGULAR = 2                           # MIP_CAND_ANGULAR: flags bit of mip_candidates_frames (angular modes are candidates)
+CAND_MAX_K = 32                            # MIP_CAND_MAX_K: the candidate lists hold 1..32 entries
 
 
 class _Opts(ctypes.Structure):
@@ -164,6 +167,8 @@ def library():
         "mip_angular_frames": (ip, [vp, vp, vp, ip, vp, ip, vp, vp, vp]),
         "mip_angular_refine_device": (ip, [vp, vp, vp, ip, vp, ip, ip, vp, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, vp]),
         "mip_angular_refine_frames": (ip, [vp, vp, vp, ip, vp, ip, ip, vp, vp, vp, vp]),
+        "mip_candidates_device": (ip, [ip, ip, ip, ip, vp, vp, ip, vp, vp, vp, ctypes.c_int32, vp, vp, vp]),
+        "mip_candidates_frames": (ip, [vp, vp, vp, ip, ip, ctypes.c_uint, vp, vp, ip, ip, ctypes.c_int32, vp, vp]),
         "mip_time_search_device": (ctypes.c_double, [vp, vp, vp, ip, vp, ip]),
         "mip_host_stats": (ip, [vp, ctypes.POINTER(ctypes.c_uint64), ip]),
         "mip_search_census": (ip, [vp, ctypes.POINTER(ctypes.c_uint64), ip]),
@@ -690,6 +695,34 @@ class MipEngine:
                                                        _ptr(tried), int(bias), _ptr(best_mode), _ptr(best_cost),
                                                        ctypes.c_void_p(s.cuda_stream)))
 
+    def candidates(self, frames, k=3, regular=True, angular=None, seeds=0, intra_bias=None, angular_bias=0, refs=None) -> dict:
+        """K-best candidate lists of host frames over the mode families (mip_candidates_frames): per
+        chunk the search with MIP lists of length min(k, 32), with `regular` the Planar / DC table,
+        with `angular` -- "all" or a mode list as in angular -- the angular table (`seeds` 0: every
+        listed mode; 1..3: angular_refine's coarse-to-fine search), then candidates_device.  dict of
+        'modes' uint8 / 'costs' int32 [F, nCTUs*5380, k]: the k lowest (cost + bias, rank) modes of
+        every CU, 0xff / UNAVAILABLE past its candidates.  intra_bias (Planar, DC) and angular_bias
+        are in 0 .. 1<<20."""
+        f = self._frames(frames)
+        r = None if refs is None else self._frames(refs)
+        n = f.shape[0]
+        flags = CAND_REGULAR if regular else 0
+        m = None
+        if angular is not None:
+            flags |= CAND_ANGULAR
+            m = None if isinstance(angular, str) and angular == "all" else _modes(angular)
+        if int(k) != k or not 1 <= int(k) <= CAND_MAX_K:
+            raise MipError("k must be an integer in 1..%d" % CAND_MAX_K)
+        if int(angular_bias) != np.clip(int(angular_bias), -(1 << 31), (1 << 31) - 1):
+            raise MipError("bias does not fit int32")
+        res = {"modes": np.empty((n, self.cus_per_frame, int(k)), np.uint8), "costs": np.empty((n, self.cus_per_frame, int(k)), np.int32)}
+        b = _bias(intra_bias)
+        with self._lock:
+            _check(library().mip_candidates_frames(self._h, _ptr(f), _ptr(r), n, int(k), flags, _ptr(b), _ptr(m),
+                                                   0 if m is None else m.size, _seeds(seeds), int(angular_bias), _ptr(res["modes"]),
+                                                   _ptr(res["costs"])))
+        return res
+
     def time_search_device(self, frames, costs, refs=None, reps=10) -> float:
         with self._lock:
             ms = library().mip_time_search_device(self._h, _ptr(frames), _ptr(refs), frames.shape[0], _ptr(costs),
@@ -759,6 +792,46 @@ def topk_device(costs, width, height, k, modes=None, costs_k=None, stream=None):
     _check(library().mip_topk_device(_ptr(costs), int(width), int(height), n, int(k), _ptr(modes), _ptr(costs_k),
                                      ctypes.c_void_p(s.cuda_stream)))
     return modes, costs_k
+
+
+def candidates_device(width, height, k, mip_mode=None, mip_cost=None, intra_cost=None, intra_bias=None, ang_cost=None, ang_bias=0,
+                      modes=None, costs=None, stream=None):
+    """K-best candidate lists over the mode families on device tensors (mip_candidates_device,
+    contract in include/mipgpu.h): the k lowest (cost + bias, rank) modes of every CU among the
+    families given -- `mip_mode` uint8 / `mip_cost` int32 [F, nCTUs*5380, kin] (the decision lists
+    of a search or of topk_device), `intra_cost` int32 [F, nCTUs*5380, 2] (intra_device's table;
+    intra_bias: Planar, DC), `ang_cost` int32 [F, nCTUs*5380, 65] (angular_device's or
+    angular_refine_device's table).  `modes` uint8 / `costs` int32 [F, nCTUs*5380, k]: pass a tensor
+    to fill it, False to leave that output out, None to have it allocated.  Returns (modes, costs)
+    (None for an output left out).  Every tensor's first dimension is F, a MIP tensor's last is
+    kin.  Asynchronous on `stream` (default: torch's current stream)."""
+    import torch
+    given = [t for t in (mip_mode, mip_cost, intra_cost, ang_cost) if t is not None]
+    if not given:
+        raise MipError("candidates: no family given")
+    if int(k) != k or not 1 <= int(k) <= CAND_MAX_K:
+        raise MipError("candidates: k must be 1..%d" % CAND_MAX_K)
+    n, ncu, k = given[0].shape[0], num_ctus(width, height) * CUS_PER_CTU, int(k)
+    kin = 0 if mip_mode is None and mip_cost is None else (mip_mode if mip_mode is not None else mip_cost).shape[-1]
+    if modes is None:
+        modes = torch.empty((n, ncu, k), dtype=torch.uint8, device=given[0].device)
+    if costs is None:
+        costs = torch.empty((n, ncu, k), dtype=torch.int32, device=given[0].device)
+    modes = None if modes is False else modes
+    costs = None if costs is False else costs
+    want = {"mip_mode": (mip_mode, kin), "mip_cost": (mip_cost, kin * 4), "intra_cost": (intra_cost, 8),
+            "ang_cost": (ang_cost, ANGULAR_MODES * 4), "modes": (modes, k), "costs": (costs, k * 4)}
+    for name, (t, size) in want.items():
+        if t is not None and (t.numel() * t.element_size() != n * ncu * size or not t.is_contiguous()):
+            raise MipError(f"candidates_device: {name} must be a contiguous tensor of {n * ncu * size} bytes")
+    if int(ang_bias) != np.clip(int(ang_bias), -(1 << 31), (1 << 31) - 1):
+        raise MipError("bias does not fit int32")
+    s = stream if stream is not None else torch.cuda.current_stream(given[0].device)
+    b = _bias(intra_bias)
+    _check(library().mip_candidates_device(int(width), int(height), n, k, _ptr(mip_mode), _ptr(mip_cost), int(kin), _ptr(intra_cost),
+                                           _ptr(b), _ptr(ang_cost), int(ang_bias), _ptr(modes), _ptr(costs),
+                                           ctypes.c_void_p(s.cuda_stream)))
+    return modes, costs
 
 
 def _penalty(penalty):
