@@ -17,9 +17,10 @@ FILTER = C.FILTER
 TABLES = ("cost", "sad", "satd")
 EVEN_MODES = tuple(range(2, 67, 2))
 
-# launch_angular (vvc-mip-gpu_amd/csrc/mip_angular.hip): grid = min(items, 32 * CUs) over the
-# intra kernel's items -- frames * CTUs * 20, per CTU the four 64x64 CUs, then the sixteen 32x32
-# blocks.  tests/test_angular_cpu.py compares the factor with the launcher's text.
+# launch_angular (vvc-mip-gpu_amd/csrc/mip_angular.hip) through launch_window_kernel
+# (vvc-mip-gpu_amd/csrc/mip_window_dev.h): grid = min(items, 32 * CUs) over the intra kernel's
+# items -- frames * CTUs * 20, per CTU the four 64x64 CUs, then the sixteen 32x32 blocks.
+# tests/test_angular_cpu.py compares the factor with that function's text.
 ANGULAR_ITEMS_PER_CU = 32
 ANGULAR_ITEMS_PER_CTU = launch_caps.INTRA_ITEMS_PER_CTU
 ANGULAR_BIG_ITEMS = launch_caps.INTRA_BIG_ITEMS

@@ -4,11 +4,14 @@ loop and a tail loop that split the work of a pass.  tests/test_gpu_multipass.py
 tests/test_gpu_predict_multipass.py and tests/test_gpu_copy.py size their work from these
 factors so that every workgroup runs at least two passes; the CPU test of
 tests/test_gpu_multipass.py reads the launchers' text and fails when a factor here no longer
-is the launcher's.
+is the launcher's.  The intra kernel and the two angular kernels have one item walk, one window
+staging and one launch rule between them, in WINDOW_HEADER: window_text() is that file, and
+uses_window_rules() says whether a launcher and its kernel go through it.
 
   launch_partition (vvc-mip-gpu_amd/csrc/mip_partition.hip): grid = min(groups, 8 * CUs),
       groups = frames * CTUs, one (frame, CTU) pair per pass;
-  launch_intra (vvc-mip-gpu_amd/csrc/mip_intra.hip): grid = min(items, 32 * CUs),
+  launch_intra (vvc-mip-gpu_amd/csrc/mip_intra.hip), through launch_window_kernel
+      (vvc-mip-gpu_amd/csrc/mip_window_dev.h): grid = min(items, 32 * CUs),
       items = frames * CTUs * 20 -- per CTU the four 64x64 CUs, then the sixteen 32x32 blocks.
   launch_predict (vvc-mip-gpu_amd/csrc/mip_predict.hip): grid = min(ceil(n / 16), 256 * 16)
       workgroups of 4 waves, a wave takes 4 consecutive list items per pass (one per 16 lanes):
@@ -38,10 +41,11 @@ COPY_GROUPS_PER_CU = 8
 COPY_WORDS_PER_GROUP = 1024     # uint4 per workgroup and iteration
 COPY_MAIN_LOOP_REACH = 768      # the main loop runs while i + 768 < n16
 
-# (source file, launcher, factor): the launcher's cap reads `groups < F * cus ? groups : F * cus`
+# (source file, function that holds the cap, factor): the cap reads `groups < F * cus ? groups : F * cus`
+WINDOW_HEADER = "mip_window_dev.h"
 LAUNCHERS = (
     ("mip_partition.hip", "launch_partition", PARTITION_GROUPS_PER_CU),
-    ("mip_intra.hip", "launch_intra", INTRA_ITEMS_PER_CU),
+    (WINDOW_HEADER, "launch_window_kernel", INTRA_ITEMS_PER_CU),
 )
 CAP_EXPRESSION = re.compile(r"grid\s*=\s*groups\s*<\s*(\d+)LL\s*\*\s*cus\s*\?\s*groups\s*:\s*(\d+)LL\s*\*\s*cus\s*;")
 
@@ -52,6 +56,19 @@ def launcher_body(source, launcher):
         text = f.read()
     at = text.index("hipError_t %s(" % launcher)
     return text[at:]
+
+
+def window_text():
+    """The header of the intra and angular kernels' shared item walk, staging and launch rules."""
+    with open(os.path.join(CSRC, WINDOW_HEADER)) as f:
+        return f.read()
+
+
+def uses_window_rules(source, launcher, kernel):
+    """`launcher` takes its argument and grid rules, `kernel` its items and staging, from WINDOW_HEADER."""
+    body, code = launcher_body(source, launcher), kernel_body(source, kernel)
+    return ("window_args_ok(a)" in body and "return launch_window_kernel(%s, a, s);" % kernel in body and "hipLaunchKernelGGL" not in body
+            and "window_item(g, a.nctus, a.ctu_cols, frame_samples, a.orig, a.refs)" in code and "stage_window(it.F, it.R, a.width," in code)
 
 
 def kernel_body(source, kernel):

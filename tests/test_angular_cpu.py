@@ -153,12 +153,14 @@ def test_one_cu_equals_the_tables_and_the_restatement_is_quick():
 
 def test_launch_cap_matches_the_launcher():
     """launch_angular caps its grid at ANGULAR_ITEMS_PER_CU workgroups per CU over the intra
-    kernel's items (the multi-pass GPU test sizes its batch from it)."""
-    body = launch_caps.launcher_body("mip_angular.hip", "launch_angular")
+    kernel's items (the multi-pass GPU test sizes its batch from it): the shared launch rule and item
+    walk of launch_caps.WINDOW_HEADER, which launcher and kernel go through."""
+    assert launch_caps.uses_window_rules("mip_angular.hip", "launch_angular", "angular_kernel")
+    body = launch_caps.launcher_body(launch_caps.WINDOW_HEADER, "launch_window_kernel")
     caps = launch_caps.CAP_EXPRESSION.findall(body)
     assert caps == [(str(AC.ANGULAR_ITEMS_PER_CU),) * 2], caps
     assert "a.nframes * a.nctus * kItemsPerCtu" in body
     kernel = launch_caps.kernel_body("mip_angular.hip", "angular_kernel")
-    assert "g += gridDim.x" in kernel and "const bool big = k < %d;" % AC.ANGULAR_BIG_ITEMS in kernel
-    with open(launch_caps.CSRC + "/mip_angular.hip") as f:
-        assert "constexpr int kItemsPerCtu = 4 + kIntraBlocks;" in f.read() and AC.ANGULAR_ITEMS_PER_CTU == 20
+    text = launch_caps.window_text()
+    assert "g += gridDim.x" in kernel and text.count("const bool big = k < %d;" % AC.ANGULAR_BIG_ITEMS) == 1
+    assert text.count("constexpr int kItemsPerCtu = 4 + kIntraBlocks;") == 1 and AC.ANGULAR_ITEMS_PER_CTU == 20

@@ -275,16 +275,23 @@ def test_entry_points_refuse_a_null_engine():
 
 def test_launch_cap_is_the_angular_launcher_s():
     """launch_angular_refine: angular_kernel's items and grid cap (tests/angular_cases.angular_cap
-    sizes the multi-pass GPU test), and angular_kernel's item walk."""
-    plain = launch_caps.launcher_body("mip_angular.hip", "launch_angular")
-    body = launch_caps.launcher_body("mip_angular_refine.hip", "launch_angular_refine")
+    sizes the multi-pass GPU test), and angular_kernel's item walk: both launchers and both kernels
+    go through the one grid rule and item walk of launch_caps.WINDOW_HEADER, and neither file has
+    a cap or an item count of its own."""
+    assert launch_caps.uses_window_rules("mip_angular.hip", "launch_angular", "angular_kernel")
+    assert launch_caps.uses_window_rules("mip_angular_refine.hip", "launch_angular_refine", "angular_refine_kernel")
+    body = launch_caps.launcher_body(launch_caps.WINDOW_HEADER, "launch_window_kernel")
     caps = launch_caps.CAP_EXPRESSION.findall(body)
-    assert caps == launch_caps.CAP_EXPRESSION.findall(plain) == [(str(AC.ANGULAR_ITEMS_PER_CU),) * 2], caps
-    assert "a.nframes * a.nctus * kItemsPerCtu" in body and "a.nframes * a.nctus * kItemsPerCtu" in plain
+    assert caps == [(str(AC.ANGULAR_ITEMS_PER_CU),) * 2], caps
+    assert "a.nframes * a.nctus * kItemsPerCtu" in body
+    for source in ("mip_angular.hip", "mip_angular_refine.hip"):
+        with open(launch_caps.CSRC + "/" + source) as f:
+            own = f.read()
+        assert not launch_caps.CAP_EXPRESSION.findall(own) and "kItemsPerCtu =" not in own and "big = k <" not in own, source
     kernel = launch_caps.kernel_body("mip_angular_refine.hip", "angular_refine_kernel")
-    assert "g += gridDim.x" in kernel and "const bool big = k < %d;" % AC.ANGULAR_BIG_ITEMS in kernel
-    with open(launch_caps.CSRC + "/mip_angular_refine.hip") as f:
-        assert "constexpr int kItemsPerCtu = 4 + kIntraBlocks;" in f.read()
+    text = launch_caps.window_text()
+    assert "g += gridDim.x" in kernel and text.count("const bool big = k < %d;" % AC.ANGULAR_BIG_ITEMS) == 1
+    assert text.count("constexpr int kItemsPerCtu = 4 + kIntraBlocks;") == 1
 
 
 def _kernel(name):

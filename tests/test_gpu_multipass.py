@@ -35,10 +35,11 @@ def test_launch_caps_are_the_launchers():
         assert len(found) == 1, (source, found)
         assert found[0] == (str(factor), str(factor)), (source, found)
         assert "hipDeviceAttributeMultiprocessorCount" in body, source
-    # the intra kernel's items per CTU, which the alternation argument of the intra test rests on
-    with open(L.CSRC + "/mip_intra.hip") as f:
-        text = f.read()
-    assert "constexpr int kItemsPerCtu = 4 + kIntraBlocks;" in text and "const bool big = k < 4;" in text
+    # the intra kernel's items per CTU, which the alternation argument of the intra test rests on:
+    # the shared walk's, which launch_intra and intra_kernel go through
+    text = L.window_text()
+    assert text.count("constexpr int kItemsPerCtu = 4 + kIntraBlocks;") == 1 and text.count("const bool big = k < 4;") == 1
+    assert L.uses_window_rules("mip_intra.hip", "launch_intra", "intra_kernel")
     with open(L.CSRC + "/intra_plan.h") as f:
         assert "constexpr int kIntraBlocks = 16;" in f.read()
     assert L.INTRA_ITEMS_PER_CTU == 4 + 16 and L.INTRA_BIG_ITEMS == 4

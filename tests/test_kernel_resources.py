@@ -13,6 +13,10 @@ objects' metadata, tests/kernel_resources.py).
 * filter_kernel: 2-D filters (128-thread tiles) <= 64 VGPRs, i.e. 8 waves per SIMD; the
   separable ones run one-wave 64-thread tiles (round 6) whose ~10 KB of LDS each allow 16 per
   CU, 4 waves per SIMD: <= 128 VGPRs.
+* intra_kernel, the first of the kernels that cost every CU from a staged window and share
+  their item walk and staging (csrc/mip_window_dev.h): <= 128 VGPRs, 4 waves per SIMD, no
+  scratch.  Its angular siblings, at 3 waves per SIMD, are pinned in
+  tests/test_angular_refine_cpu.py.
 """
 import os
 import re
@@ -71,3 +75,11 @@ def test_filter_kernel_occupancy(kernels):
     for name, k in _named(kernels, "filter_kernel").items():
         sep = re.search(r"filter_kernelILi\dELb\dELb(\d)EE", name).group(1) == "1"  # <RAD, FLOAT, SEP>
         assert k[".vgpr_count"] <= (128 if sep else 64), (name, k[".vgpr_count"])
+
+
+def test_intra_kernel_occupancy(kernels):
+    found = {n: k for n, k in kernels.items() if re.search(r"\d+intra_kernelE", n)}
+    assert len(found) == 1, found
+    (name, k), = found.items()
+    assert k[".vgpr_count"] + k.get(".agpr_count", 0) <= 128, (name, k[".vgpr_count"])
+    assert k[".private_segment_fixed_size"] == 0 and k.get(".vgpr_spill_count", 0) == 0, name

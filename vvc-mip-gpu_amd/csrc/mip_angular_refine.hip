@@ -1,7 +1,8 @@
 // mip_angular_refine.hip -- coarse-to-fine angular mode search in one launch (gfx950), contract in
 // include/mipgpu.h (mip_angular_refine_device).  No reference counterpart.  A second kernel beside
 // angular_kernel (mip_angular.hip), which stays as it is: the same items, window staging, lane
-// slots and grid cap, so one staging of a window serves both passes.
+// slots and grid cap (mip_window_dev.h) and the same steps of the two paths (mip_angular_dev.h), so
+// one staging of a window serves both passes.
 //
 // Coarse pass: angular_kernel's loop over the caller's list (scalar modes from the kernel
 // arguments, two per round).  After the xor butterfly every lane of a group holds the group's
@@ -25,7 +26,6 @@
 namespace mipgpu {
 namespace {
 
-constexpr int kItemsPerCtu = 4 + kIntraBlocks;
 constexpr int kMaxCand = 2 * kAngMaxSeeds;
 
 // The packed (mode, angle, inverse) word of a mode chosen on the device.  The mode is clamped
@@ -41,14 +41,11 @@ __device__ __forceinline__ uint32_t mode_word(const uint32_t *s_pack, int m) {
 
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3, 3))) void angular_refine_kernel(AngularRefineArgs a) {
   __shared__ __attribute__((aligned(16))) uint16_t s_org[64 * 64];
-  __shared__ __attribute__((aligned(16))) uint16_t s_ref[kLeftAt + 65 + 7];
-  static_assert(kConstAt > kLeftAt + 64 && kConstAt < kLeftAt + 65 + 7, "the constant's cell lies behind s_left");
-  uint16_t *const s_left = s_ref + kLeftAt;
-  __shared__ int s_sum[kThreads / 64][kAngModes][2];  // 64x64 CU: the waves' (sad, satd) per list entry, then per candidate
-  __shared__ int s_tab[3][kAngModes];                 // 64x64 CU: cost, sad, satd per table slot
+  __shared__ __attribute__((aligned(16))) uint16_t s_ref[kRefCells];
+  __shared__ WaveSums s_sum[kThreads / 64];           // 64x64 CU: the waves' (sad, satd) per list entry, then per candidate
+  __shared__ CuTable s_tab[3];                        // 64x64 CU: cost, sad, satd per table slot
   __shared__ uint32_t s_pack[kAngModes];              // ang_pack of every mode, slot = mode - 2
   __shared__ int s_cand[kMaxCand + 1];                // 64x64 CU: the modes of the refinement rounds, then their count
-  static_assert(kRefRows64 * 64 <= kRefRows32 * 32, "the 64x64 CU's reference rows fit");
   static_assert(kMaxCand <= kAngModes, "the candidates' sums fit s_sum");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long long frame_samples = (long long)a.width * a.height;
@@ -58,38 +55,20 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3, 3))
   const int rounds = 2 * a.nseeds;  // (uniform over the grid)
   if (tid < kAngModes) s_pack[tid] = a.all[tid];  // (the first item's barriers order it before its readers)
   for (long long g = blockIdx.x; g < items; g += gridDim.x) {
-    const long long fc = g / kItemsPerCtu;  // frame * nctus + ctu
-    const int k = (int)(g - fc * kItemsPerCtu), frame = (int)(fc / a.nctus), ctu = (int)(fc - (long long)frame * a.nctus);
-    const bool big = k < 4;
-    const int lp = big ? 6 : 5, side = 1 << lp;
-    const int x0 = 128 * (ctu % a.ctu_cols) + (big ? 64 * (k & 1) : 32 * ((k - 4) & 3));
-    const int y0 = 128 * (ctu / a.ctu_cols) + (big ? 64 * (k >> 1) : 32 * ((k - 4) >> 2));
-    const uint16_t *F = a.orig + (size_t)frame * frame_samples, *R = a.refs + (size_t)frame * frame_samples;
+    const WindowItem it = window_item(g, a.nctus, a.ctu_cols, frame_samples, a.orig, a.refs);
     __syncthreads();  // (the previous item's last reads of the window, of s_tab and of s_cand)
-    for (int i = tid; i < side * side; i += kThreads) {
-      const long long idx = (long long)(y0 + (i >> lp)) * a.width + x0 + (i & (side - 1));
-      s_org[i] = idx < frame_samples ? F[idx] : (uint16_t)0;
-    }
-    const int rows = big ? kRefRows64 : kRefRows32;
-    for (int i = tid; i < rows * side; i += kThreads) {
-      const int r = i >> lp;
-      const long long idx = (long long)(y0 - 1 + r) * a.width + x0 + (i & (side - 1));
-      s_ref[i] = idx >= 0 && idx < frame_samples ? R[idx] : (uint16_t)0;
-    }
-    if (tid <= side) {  // rows y0-1 .. y0+side-1 of column x0-1
-      const long long idx = (long long)(y0 - 1 + tid) * a.width + x0 - 1;
-      s_left[tid] = idx >= 0 && idx < frame_samples ? R[idx] : (uint16_t)0;
-    }
+    stage_window(it.F, it.R, a.width, frame_samples, it.x0, it.y0, it.lp, it.big, tid, s_org, s_ref);
     if (tid == 0) s_ref[kConstAt] = 512;
-    if (big && tid < kAngModes) s_tab[0][tid] = s_tab[1][tid] = s_tab[2][tid] = none;
+    reset_table(s_tab, it.big, tid);
     __syncthreads();
-    const LdsRef ref{s_ref, x0, y0, lp};
-    const size_t cu_base = (size_t)fc * MIP_CUS_PER_CTU;
+    const LdsRef ref{s_ref, it.x0, it.y0, it.lp};
+    const size_t cu_base = (size_t)it.fc * MIP_CUS_PER_CTU;
     int org[16];
-    if (big) {  // 256 lanes, one CU: wave sums per mode, then the four waves' through LDS
+    if (it.big) {  // 256 lanes, one CU: wave sums per mode, then the four waves' through LDS
+      const int k = it.k;
       const IntraSlot c{k, tid & 15, tid >> 4, 0, 0, 6, 6};
-      load_org(s_org, lp, c, org);
-      const LdsBound b(ref, x0, y0, 64, 64);
+      load_org(s_org, it.lp, c, org);
+      const LdsBound b(ref, it.x0, it.y0, 64, 64);
       const int corner = b.corner();
       for (int q = 0; q < a.nmodes; q++) {
         int v[2];
@@ -98,20 +77,13 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3, 3))
         if (lane == 0) s_sum[wave][q][0] = v[0], s_sum[wave][q][1] = v[1];
       }
       __syncthreads();
-      const bool on = !a.unavail[(size_t)ctu * MIP_CUS_PER_CTU + k];
-      auto finish = [&](int q, int slot) {  // the four waves' sums of entry q into table slot `slot`
-        const int sad = s_sum[0][q][0] + s_sum[1][q][0] + s_sum[2][q][0] + s_sum[3][q][0];
-        const int satd = s_sum[0][q][1] + s_sum[1][q][1] + s_sum[2][q][1] + s_sum[3][q][1];
-        s_tab[0][slot] = intra_cost(sad, satd);
-        s_tab[1][slot] = sad;
-        s_tab[2][slot] = satd;
-      };
+      const bool on = !a.unavail[(size_t)it.ctu * MIP_CUS_PER_CTU + k];
       // (t is tid, opaque per item: the per-lane addresses of this path -- a.modes[t], the tables'
       // a.cost + t -- are otherwise hoisted out of the item loop into registers held across the
       // 32x32 path, which at three waves per SIMD has none to spare)
       int t = tid;
       asm volatile("" : "+v"(t));
-      if (t < a.nmodes && on) finish(t, ang_unpack(a.modes[t]).m - MIP_ANGULAR_FIRST);
+      if (t < a.nmodes && on) finish_slot(s_sum, s_tab, t, ang_unpack(a.modes[t]).m - MIP_ANGULAR_FIRST);
       __syncthreads();
       // one lane: the seeds and the candidates of the CU (none if it is unavailable: every cost is
       // then MIP_COST_UNAVAILABLE and the top list stays empty); rounds past the set's end get
@@ -139,14 +111,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3, 3))
         if (lane == 0) s_sum[wave][r][0] = v[0], s_sum[wave][r][1] = v[1];
       }
       __syncthreads();
-      if (tid < ncand && on) finish(tid, (int)(mode_word(s_pack, s_cand[tid]) & 0xffu) - MIP_ANGULAR_FIRST);
+      if (tid < ncand && on) finish_slot(s_sum, s_tab, tid, (int)(mode_word(s_pack, s_cand[tid]) & 0xffu) - MIP_ANGULAR_FIRST);
       __syncthreads();
       const size_t cu = cu_base + k;
-      if (t < kAngModes) {
-        if (a.cost) a.cost[cu * kAngModes + t] = s_tab[0][t];
-        if (a.sad) a.sad[cu * kAngModes + t] = s_tab[1][t];
-        if (a.satd) a.satd[cu * kAngModes + t] = s_tab[2][t];
-      }
+      flush_table(s_tab, t, cu, a.cost, a.sad, a.satd);
       if (tid == 0) {
         uint8_t mode = 0xff;
         int32_t cost = none;
@@ -161,49 +129,31 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3, 3))
         if (a.tried) a.tried[cu] = (uint8_t)(on ? a.nmodes + ncand : 0);
       }
     } else {
-      const uint32_t *slots = a.slots + (size_t)(k - 4) * a.slots_per_block;
+      const uint32_t *slots = a.slots + (size_t)(it.k - 4) * a.slots_per_block;
       for (int at = 64 * wave; at < a.slots_per_block; at += kThreads) {
-        const uint32_t word = slots[at + lane];
-        const IntraSlot c = intra_slot_decode(word);  // (no slot: fields of CU 0 at the window's corner, nothing written)
-        const int n = 1 << (c.lw + c.lh - 4);
-        load_org(s_org, lp, c, org);
-        const LdsBound b(ref, x0 + 4 * c.cx, y0 + 4 * c.cy, 1 << c.lw, 1 << c.lh);
+        const SlotCu s = slot_cu(slots[at + lane], a.unavail, it.ctu, cu_base);
+        load_org(s_org, it.lp, s.c, org);
+        const LdsBound b(ref, it.x0 + 4 * s.c.cx, it.y0 + 4 * s.c.cy, 1 << s.c.lw, 1 << s.c.lh);
         const int corner = b.corner();
-        const bool first = !(word & kIntraNoSlot) && (c.bi | c.bj) == 0;  // the lane that writes the CU
-        const bool on = first && !a.unavail[(size_t)ctu * MIP_CUS_PER_CTU + c.cu];
-        const size_t cu = cu_base + c.cu;
-        if (tables && first) {  // slots of modes not in the list (a candidate's is written again below), every slot of an unavailable CU
-          for (int slot = 0; slot < kAngModes; slot++)
-            if (!on || !ang_listed(a.listed, slot)) {
-              if (a.cost) a.cost[cu * kAngModes + slot] = none;
-              if (a.sad) a.sad[cu * kAngModes + slot] = none;
-              if (a.satd) a.satd[cu * kAngModes + slot] = none;
-            }
-        }
+        if (tables && s.first) clear_unlisted(a.cost, a.sad, a.satd, s.cu, s.on, a.listed);  // (a candidate's slot is written again below)
         AngTop top = ang_top_none();  // (every lane of the group: the sums are the group's in each)
-        auto take = [&](int m, int sad, int satd) {
-          const size_t to = cu * kAngModes + m - MIP_ANGULAR_FIRST;
-          if (a.cost) a.cost[to] = intra_cost(sad, satd);
-          if (a.sad) a.sad[to] = sad;
-          if (a.satd) a.satd[to] = satd;
-        };
         for (int q = 0; q < a.nmodes; q += 2) {
           const bool two = q + 1 < a.nmodes;
           const AngMode m0 = ang_unpack(a.modes[q]), m1 = ang_unpack(a.modes[two ? q + 1 : q]);
           int v[4] = {0, 0, 0, 0};
-          ang_block(b, m0, corner, c.lw, c.lh, 4 * c.bi, 4 * c.bj, org, v[0], v[1]);
-          if (two) ang_block(b, m1, corner, c.lw, c.lh, 4 * c.bi, 4 * c.bj, org, v[2], v[3]);
-          group_sum(v, n);
+          ang_block(b, m0, corner, s.c.lw, s.c.lh, 4 * s.c.bi, 4 * s.c.bj, org, v[0], v[1]);
+          if (two) ang_block(b, m1, corner, s.c.lw, s.c.lh, 4 * s.c.bi, 4 * s.c.bj, org, v[2], v[3]);
+          group_sum(v, s.n);
           ang_top_step(top, m0.m, intra_cost(v[0], v[1]));
           if (two) ang_top_step(top, m1.m, intra_cost(v[2], v[3]));
-          if (on) {
-            take(m0.m, v[0], v[1]);
-            if (two) take(m1.m, v[2], v[3]);
+          if (s.on) {
+            write_slot(a.cost, a.sad, a.satd, s.cu, m0.m, v[0], v[1]);
+            if (two) write_slot(a.cost, a.sad, a.satd, s.cu, m1.m, v[2], v[3]);
           }
         }
         // the best of the list is the top list's first entry; the other entries end in the set
         AngSet cand = ang_candidates(top, a.nseeds, a.listed);
-        if (first && a.tried) a.tried[cu] = (uint8_t)(on ? a.nmodes + ang_set_count(cand) : 0);
+        if (s.first && a.tried) a.tried[s.cu] = (uint8_t)(s.on ? a.nmodes + ang_set_count(cand) : 0);
         const int seed = top.m0;
         uint8_t best_mode = (uint8_t)MIP_MODE_ANGULAR(seed);
         int32_t best_cost = top.c0;
@@ -211,12 +161,12 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3, 3))
           const int next = ang_set_pop(cand);
           const AngMode md = ang_unpack(mode_word(s_pack, next ? next : seed));
           int v[2] = {0, 0};
-          ang_block(b, md, corner, c.lw, c.lh, 4 * c.bi, 4 * c.bj, org, v[0], v[1]);
-          group_sum(v, n);
+          ang_block(b, md, corner, s.c.lw, s.c.lh, 4 * s.c.bi, 4 * s.c.bj, org, v[0], v[1]);
+          group_sum(v, s.n);
           if (next) ang_best_step_any(best_mode, best_cost, md.m, intra_cost(v[0], v[1]));
-          if (on && next) take(md.m, v[0], v[1]);
+          if (s.on && next) write_slot(a.cost, a.sad, a.satd, s.cu, md.m, v[0], v[1]);
         }
-        if (first) write_best(a, cu, on, on ? best_mode : (uint8_t)0xff, on ? best_cost : none);
+        if (s.first) write_best(a, s.cu, s.on, s.on ? best_mode : (uint8_t)0xff, s.on ? best_cost : none);
       }
     }
   }
@@ -225,19 +175,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3, 3))
 }  // namespace
 
 hipError_t launch_angular_refine(const AngularRefineArgs &a, hipStream_t s) {
-  const long long groups = (long long)a.nframes * a.nctus * kItemsPerCtu;
-  if (!a.orig || !a.refs || !a.unavail || !a.slots || a.nframes < 1 || a.nctus < 1 || a.ctu_cols < 1 || a.slots_per_block < 64 ||
-      a.slots_per_block % 64 || (long long)a.nframes * a.nctus * MIP_CUS_PER_CTU > (1LL << 31) - 256 || a.nmodes < 1 ||
-      a.nmodes > kAngModes || a.nseeds < 1 || a.nseeds > kAngMaxSeeds || a.nseeds > a.nmodes || !a.best_cost != !a.best_mode ||
+  if (!window_args_ok(a) || a.nmodes < 1 || a.nmodes > kAngModes || a.nseeds < 1 || a.nseeds > kAngMaxSeeds || a.nseeds > a.nmodes ||
       !a.ang_cost != !a.ang_mode || (!a.cost && !a.sad && !a.satd && !a.best_cost && !a.ang_cost && !a.tried))
     return hipErrorInvalidValue;
-  // a few rounds of resident workgroups, each striding over the items
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-    return hipErrorInvalidDevice;
-  const long long grid = groups < 32LL * cus ? groups : 32LL * cus;
-  hipLaunchKernelGGL(angular_refine_kernel, dim3((unsigned)grid), dim3(kThreads), 0, s, a);
-  return hipGetLastError();
+  return launch_window_kernel(angular_refine_kernel, a, s);
 }
 
 }  // namespace mipgpu

@@ -2,57 +2,17 @@
 // (gfx950), contract in include/mipgpu.h (mip_intra_device).  No reference counterpart: the
 // reference ranks MIP modes only.  The arithmetic is intra_plan.h's, shared with the host walk.
 //
-// Work items are (frame, CTU, k): k < 4 the 64x64 CU of quadrant k, else the 32x32 block
-// k - 4, which holds 336 CUs of the other 46 shapes.  A workgroup (4 waves) takes items
-// blockIdx.x, + gridDim.x, ...; per item it stages the window's originals and reference
-// samples once, by linear index with the guard idx < W*H (2-byte loads: no alignment demand on
-// the caller's frames), as uint16 in LDS:
-//   s_org   S x S originals                        (S = 32 or 64)
-//   s_ref   rows y0-1 .. y0+S-1 of columns x0 .. x0+S-1   (64x64: rows y0-1 and y0 only)
-//   s_left  column x0-1 of the same rows
-// and then walks the block's lane slots (intra_plan.h intra_build_slots): one lane per 4x4
-// block of a CU, a CU's lanes an aligned power-of-two group of one wave.  A lane builds both
-// modes' 16 residuals in registers and runs the Hadamard in-lane; the DC sums and the four
-// per-CU sums are xor-shuffle reductions inside the group (the 64x64 CU's 256 lanes finish
-// through LDS).  The group's first lane writes the CU's two costs per table with one 8-byte
-// store and merges the CU's decision.  No atomics; every index comes from the slot table and
-// the work-item index, sample values are only ever values.  DESIGN.md section 5.6.
-#include "intra_plan.h"
-#include "mip_kernels.h"
+// Work items, window staging, the window Ref and the group sum are mip_window_dev.h's, shared with
+// the angular kernels.  Per lane slot a lane builds both modes' 16 residuals in registers and runs
+// the Hadamard in-lane; the DC sums and the four per-CU sums are xor-shuffle reductions inside the
+// group (the 64x64 CU's 256 lanes finish through LDS).  The group's first lane writes the CU's
+// two costs per table with one 8-byte store and merges the CU's decision.  No atomics; every
+// index comes from the slot table and the work-item index, sample values are only ever values.
+// DESIGN.md section 5.6.
+#include "mip_window_dev.h"
 
 namespace mipgpu {
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kItemsPerCtu = 4 + kIntraBlocks;
-constexpr int kRefRows32 = 33, kRefRows64 = 2;
-constexpr int kLeftAt = kRefRows32 * 32;  // s_left inside the reference array
-
-// The staged window as a Ref of intra_plan.h.
-struct LdsRef {
-  const uint16_t *ref;  // s_ref, with s_left at kLeftAt (one array: one index, no pointer select)
-  int x0, y0, lp;       // the window's frame position, log2 of its side
-  __device__ __forceinline__ int operator()(int row, int col) const {
-    const int r = row - y0 + 1;
-    return ref[col >= x0 ? (r << lp) + col - x0 : kLeftAt + r];
-  }
-};
-
-// Sums of K values over the lane's group of n lanes (a power of two, the group aligned): every
-// lane runs all six steps and keeps only those inside its group -- branch-free, the K chains of a
-// step independent.  (Skipping the steps no lane of the wave needs, by a wave-uniform bound, was
-// not faster: DESIGN.md section 5.6.)
-template <int K>
-__device__ __forceinline__ void group_sum(int (&v)[K], int n) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) {
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-      const int o = __shfl_xor(v[k], m, 64);
-      v[k] += m < n ? o : 0;
-    }
-  }
-}
 
 // One lane's 4x4 block of the CU at window position (4 cx, 4 cy): the block's inputs but the DC
 // value, and the lane's share of the boundary sums.
@@ -73,15 +33,7 @@ __device__ __forceinline__ void load_block(const LdsRef &ref, const uint16_t *s_
   b.bl = intra_left(ref, x, y, (1 << c.lh) - 1);
   if (c.bj) sum_top = 0;   // the top row of blocks carries the top boundary,
   if (c.bi) sum_left = 0;  // the left column the left one
-  const uint16_t *o = s_org + ((4 * c.cy + b.j0) << ref.lp) + 4 * c.cx + b.i0;
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    const uint2 v = *reinterpret_cast<const uint2 *>(o + (r << ref.lp));
-    org[4 * r] = (int)(v.x & 0xffffu);
-    org[4 * r + 1] = (int)(v.x >> 16);
-    org[4 * r + 2] = (int)(v.y & 0xffffu);
-    org[4 * r + 3] = (int)(v.y >> 16);
-  }
+  load_org(s_org + ((4 * c.cy + b.j0) << ref.lp) + 4 * c.cx + b.i0, ref.lp, org);
 }
 
 // The CU's results: its table entries and its decision.  One lane per CU.
@@ -105,42 +57,22 @@ __device__ __forceinline__ void write_cu(const IntraArgs &a, size_t cu, bool on,
 
 __global__ __launch_bounds__(kThreads) void intra_kernel(IntraArgs a) {
   __shared__ __attribute__((aligned(16))) uint16_t s_org[64 * 64];
-  __shared__ __attribute__((aligned(16))) uint16_t s_ref[kLeftAt + 65 + 7];
-  uint16_t *const s_left = s_ref + kLeftAt;
+  __shared__ __attribute__((aligned(16))) uint16_t s_ref[kRefCells];
   __shared__ int s_part[kThreads / 64][6];
-  static_assert(kRefRows64 * 64 <= kRefRows32 * 32, "the 64x64 CU's reference rows fit");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long long frame_samples = (long long)a.width * a.height;
   const long long items = (long long)a.nframes * a.nctus * kItemsPerCtu;
   for (long long g = blockIdx.x; g < items; g += gridDim.x) {
-    const long long fc = g / kItemsPerCtu;  // frame * nctus + ctu
-    const int k = (int)(g - fc * kItemsPerCtu), frame = (int)(fc / a.nctus), ctu = (int)(fc - (long long)frame * a.nctus);
-    const bool big = k < 4;
-    const int lp = big ? 6 : 5, side = 1 << lp;
-    const int x0 = 128 * (ctu % a.ctu_cols) + (big ? 64 * (k & 1) : 32 * ((k - 4) & 3));
-    const int y0 = 128 * (ctu / a.ctu_cols) + (big ? 64 * (k >> 1) : 32 * ((k - 4) >> 2));
-    const uint16_t *F = a.orig + (size_t)frame * frame_samples, *R = a.refs + (size_t)frame * frame_samples;
+    const WindowItem it = window_item(g, a.nctus, a.ctu_cols, frame_samples, a.orig, a.refs);
+    const int k = it.k, ctu = it.ctu;
     __syncthreads();  // (the previous item's last reads of the window)
-    for (int i = tid; i < side * side; i += kThreads) {
-      const long long idx = (long long)(y0 + (i >> lp)) * a.width + x0 + (i & (side - 1));
-      s_org[i] = idx < frame_samples ? F[idx] : (uint16_t)0;
-    }
-    const int rows = big ? kRefRows64 : kRefRows32;
-    for (int i = tid; i < rows * side; i += kThreads) {
-      const int r = i >> lp;
-      const long long idx = (long long)(y0 - 1 + r) * a.width + x0 + (i & (side - 1));
-      s_ref[i] = idx >= 0 && idx < frame_samples ? R[idx] : (uint16_t)0;
-    }
-    if (tid <= side) {  // rows y0-1 .. y0+side-1 of column x0-1
-      const long long idx = (long long)(y0 - 1 + tid) * a.width + x0 - 1;
-      s_left[tid] = idx >= 0 && idx < frame_samples ? R[idx] : (uint16_t)0;
-    }
+    stage_window(it.F, it.R, a.width, frame_samples, it.x0, it.y0, it.lp, it.big, tid, s_org, s_ref);
     __syncthreads();
-    const LdsRef ref{s_ref, x0, y0, lp};
-    const size_t cu_base = (size_t)fc * MIP_CUS_PER_CTU;
+    const LdsRef ref{s_ref, it.x0, it.y0, it.lp};
+    const size_t cu_base = (size_t)it.fc * MIP_CUS_PER_CTU;
     IntraBlock b;
     int org[16], st, sl;
-    if (big) {  // 256 lanes, one CU: wave sums, then the four waves' through LDS
+    if (it.big) {  // 256 lanes, one CU: wave sums, then the four waves' through LDS
       const IntraSlot c{k, tid & 15, tid >> 4, 0, 0, 6, 6};
       load_block(ref, s_org, c, b, org, st, sl);
       int bs[2] = {st, sl};
@@ -185,18 +117,8 @@ __global__ __launch_bounds__(kThreads) void intra_kernel(IntraArgs a) {
 }  // namespace
 
 hipError_t launch_intra(const IntraArgs &a, hipStream_t s) {
-  const long long groups = (long long)a.nframes * a.nctus * kItemsPerCtu;
-  if (!a.orig || !a.refs || !a.unavail || !a.slots || a.nframes < 1 || a.nctus < 1 || a.ctu_cols < 1 || a.slots_per_block < 64 ||
-      a.slots_per_block % 64 || (long long)a.nframes * a.nctus * MIP_CUS_PER_CTU > (1LL << 31) - 256 || !a.best_cost != !a.best_mode ||
-      (!a.cost && !a.sad && !a.satd && !a.best_cost))
-    return hipErrorInvalidValue;
-  // a few rounds of resident workgroups, each striding over the items
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-    return hipErrorInvalidDevice;
-  const long long grid = groups < 32LL * cus ? groups : 32LL * cus;
-  hipLaunchKernelGGL(intra_kernel, dim3((unsigned)grid), dim3(kThreads), 0, s, a);
-  return hipGetLastError();
+  if (!window_args_ok(a) || (!a.cost && !a.sad && !a.satd && !a.best_cost)) return hipErrorInvalidValue;
+  return launch_window_kernel(intra_kernel, a, s);
 }
 
 }  // namespace mipgpu
