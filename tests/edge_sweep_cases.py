@@ -1,13 +1,17 @@
-"""Inputs and references of the residue sweep through the intra, angular, merge, partition and
-predict kernels (tests/test_gpu_edge_sweep.py, tests/test_gpu_angular_sweep.py) -- a helper, not a
-test.  The sizes are tests/size_sweep.py's; every reference is one of the independent restatements
-(tests/intra_ref.py, tests/angular_ref.py, tests/partition_ref.py, tests/predict_ref.py, the C
-oracle), computed once (lru_cache) and shared; callers do not modify the arrays."""
+"""Inputs and references of the residue sweep through the intra, angular, refined angular, merge,
+partition, predict and candidate kernels (tests/test_gpu_edge_sweep.py,
+tests/test_gpu_angular_sweep.py, tests/test_gpu_refine_sweep.py) -- a helper, not a test.  The
+sizes are tests/size_sweep.py's; every reference is one of the independent restatements
+(tests/intra_ref.py, tests/angular_ref.py, tests/angular_refine_ref.py, tests/candidates_ref.py,
+tests/partition_ref.py, tests/predict_ref.py, the C oracle), computed once (lru_cache) and shared;
+callers do not modify the arrays."""
 from functools import lru_cache
 
 import numpy as np
 
 import angular_ref as A
+import angular_refine_ref as RR
+import candidates_ref as K
 import intra_ref as I
 import mipgpu
 import oracle_lib as O
@@ -129,12 +133,17 @@ SWEEP_MODES = (2, 10, 18, 19, 26, 33, 34, 35, 42, 50, 51, 58, 66)
 ANGULAR_CHAIN_BIAS = 60
 
 
-@lru_cache(maxsize=None)
 def angular_sweep_case(w, h, kind="noise", filt=None, modes=SWEEP_MODES):
     """(frame [H, W], references, availability set, dict of the tables of tests/angular_ref.py
     [nCTUs*5380, 65] plus 'ang_mode' / 'ang_cost' [nCTUs*5380]) of intra_case's frame for the mode
     list `modes` (a tuple; None: all 65): the frame, the oracle's filter and the set are
-    intra_case's own, computed once for both sweeps."""
+    intra_case's own, computed once for all sweeps (one cache entry however the arguments are
+    spelled)."""
+    return _angular_sweep_case(w, h, kind, filt, None if modes is None else tuple(modes))
+
+
+@lru_cache(maxsize=None)
+def _angular_sweep_case(w, h, kind, filt, modes):
     frame, refs, un, _ = intra_case(w, h, kind, filt)
     tabs = A.tables(frame, refs, un, modes)
     tabs["ang_mode"], tabs["ang_cost"] = A.best(tabs["cost"])
@@ -214,3 +223,124 @@ def angular_chain_case(w, h):
                **{k: ref[k] for k in ("ctu_cost", "ctu_leaves", "items")})
     _freeze(*out.values())
     return out
+
+
+# ---------------------------------------------------------------- the refined angular kernel's sweep
+# (list, seeds) of sweep size i is REFINE_ROTATION[i % 7].  The list of one mode has
+# nmodes == nseeds (the launcher's limit case) and a coarse round that is half empty; with (2, 66)
+# every candidate is 3 or 65.  tests/test_gpu_refine_sweep.py holds the rotation to what it reaches.
+REFINE_ROTATION = ((SWEEP_MODES, 1), (RR.EVEN_MODES, 2), (RR.ODD_MODES, 3), ((34,), 1), (RR.SPARSE_MODES, 3), ((2, 66), 2),
+                   (RR.EVEN_MODES, 1))
+# On a noise frame with original references every boundary of the CUs at (0, 0) is the 512
+# substitute and all modes tie: the seeds are 17, 19, 49, the candidates 16, 18, 20, 48, 50 -- both
+# PDPC modes as per-lane candidates on substituted lines -- and mode 16 wins with 9 modes tried.
+PDPC_TIE_CONFIG = ((17, 19, 49, 51), 3)
+PDPC_TIE_SIZES = ((148, 148), (20, 20), (124, 4))
+OTHER_CONFIG = (RR.EVEN_MODES, 2)                              # of the six filters at OTHER_SIZE
+# the candidate chain: Planar / DC and the refined angular stage, as tests/test_gpu_candidates.py
+CAND_K, CAND_ANGULAR, CAND_INTRA_BIAS, CAND_ANGULAR_BIAS = 3, (RR.EVEN_MODES, 2), (3, 5), 9
+# the host calls' cut case (tests/test_gpu_angular_sweep.py's): 200 one-CTU frames of period 3
+CUT_SIZE, CUT_FRAMES, CUT_PERIOD = (60, 52), 200, 3
+TABLE_BYTES = 256 << 20                                        # kAngularTableBytes of csrc/host_policy.h
+
+
+def refine_config(size):
+    """(list, seeds) of a sweep size, by its index in tests/size_sweep.py; OTHER_CONFIG at OTHER_SIZE."""
+    return OTHER_CONFIG if size == OTHER_SIZE else REFINE_ROTATION[S.ALL_SIZES.index(size) % len(REFINE_ROTATION)]
+
+
+@lru_cache(maxsize=None)
+def refine_sweep_case(w, h, kind, filt, modes, seeds):
+    """(frame, references, availability set, tests/angular_refine_ref.py's refine) of
+    angular_sweep_case(w, h, kind, filt, None)'s 65-mode tables for the list `modes` (a tuple) and
+    `seeds`."""
+    frame, refs, un, tabs = angular_sweep_case(w, h, kind, filt, None)
+    out = RR.refine({k: tabs[k] for k in TABLES}, modes, seeds)
+    _freeze(*out.values())
+    return frame, refs, un, out
+
+
+def candidate_wins(r):
+    """bool per CU of a refine result: the ang pair's mode is one of the CU's candidates."""
+    slot = np.clip(r["ang_mode"].astype(int) - A.MODE_BASE - A.FIRST, 0, A.MODES - 1)
+    return (r["tried"] > 0) & np.take_along_axis(r["cand"], slot[..., None], axis=-1)[..., 0]
+
+
+REFINE_CONDITIONS = ("pdpc_first_column", "pdpc_first_row", "wins_wrapped", "wins_first_column", "wins_first_row", "big_full", "big_fewer",
+                     "big_mixed_sizes", "end_candidates")
+
+
+def refine_conditions(w, h, modes, seeds, r, un):
+    """What the refined sweep is about, counted for one size from the restatement `r` alone: dict
+    of REFINE_CONDITIONS -> CUs (big_mixed_sizes: 1 if the launch holds an available and an
+    unavailable 64x64 CU)."""
+    x, y, bw, bh = geometry(w, h)
+    ok, cand = ~un, r["cand"]
+    pdpc = ok & (cand[:, 18 - A.FIRST] | cand[:, 50 - A.FIRST])
+    wins = candidate_wins(r)
+    big = (bw == 64) & (bh == 64)
+    n = cand.sum(axis=-1)
+    full = 2 * min(seeds, len(modes))
+    return {"pdpc_first_column": int((pdpc & (x == 0) & (y > 0)).sum()), "pdpc_first_row": int((pdpc & (y == 0) & (x > 0)).sum()),
+            "wins_wrapped": int((wins & wrapped(w, h)).sum()), "wins_first_column": int((wins & (x == 0)).sum()),
+            "wins_first_row": int((wins & (y == 0)).sum()), "big_full": int((big & ok & (n == full)).sum()),
+            "big_fewer": int((big & ok & (n < full)).sum()), "big_mixed_sizes": int((big & ok).any() and (big & un).any()),
+            "end_candidates": int((ok & (cand[:, 0] | cand[:, A.MODES - 1])).sum())}
+
+
+def table_cut_chunk(bytes_per_frame):
+    """Frames per chunk of a host call whose device tables take bytes_per_frame (stage_chunk_frames
+    of csrc/host_policy.h for max_batch >= the call's frames)."""
+    return TABLE_BYTES // bytes_per_frame
+
+
+def refine_cut_bytes():
+    return layout.num_ctus(*CUT_SIZE) * layout.CUS_PER_CTU * A.MODES * 4     # the cost table; `tried` does not count
+
+
+def candidates_cut_bytes(k):
+    """Per frame of mip_candidates_frames with Planar / DC and angular on a best_k 1 engine: the
+    MIP cost table (none for k = 1: the search's own decisions), the Planar / DC table, the angular one."""
+    nct = layout.num_ctus(*CUT_SIZE)
+    ncu = nct * layout.CUS_PER_CTU
+    return (nct * layout.COSTS_PER_CTU * 4 if k > 1 else 0) + ncu * 2 * 4 + ncu * A.MODES * 4
+
+
+@lru_cache(maxsize=None)
+def cut_case():
+    """(base frames [3, H, W], availability set, per base frame the refined result (even list, two
+    seeds), per base frame the candidate lists (modes, costs) of CAND_K) of the cut case."""
+    w, h = CUT_SIZE
+    un = mipgpu.unavailable_cus(w, h)
+    base = np.stack([S.content("noise", w, h, salt) for salt in range(CUT_PERIOD)])
+    nct = layout.num_ctus(w, h)
+    fine, lists = [], []
+    for f in base:
+        r = RR.refine(A.tables(f, f, un), *CAND_ANGULAR)
+        mip = layout.topk_modes(O.search(f), nct, CAND_K)
+        lists.append(K.candidates(CAND_K, mip[0], mip[1], I.tables(f, f, un)["cost"], CAND_INTRA_BIAS, r["cost"], CAND_ANGULAR_BIAS))
+        fine.append(r)
+        _freeze(*r.values(), *lists[-1])
+    _freeze(base, un)
+    return base, un, fine, lists
+
+
+@lru_cache(maxsize=None)
+def candidates_case(w, h, filt=None):
+    """(frame, availability set, modes uint8 / costs int32 [nCTUs*5380, CAND_K], the three input
+    tables) of the `edges` frame of a size: tests/candidates_ref.py over the C oracle's search as
+    lists of CAND_K (layout.topk_modes; with a filter the engine's UNAVAILABLE entries filled in),
+    tests/intra_ref.py's table and the refined angular table (CAND_ANGULAR), all on the oracle's
+    filter `filt` of the frame with that filter's availability set."""
+    frame, _, un, intra = intra_case(w, h, "edges", filt)
+    fine = refine_sweep_case(w, h, "edges", filt, *CAND_ANGULAR)[3]
+    mip_mode, mip_cost = layout.topk_modes(O.engine_search(frame, filt), layout.num_ctus(w, h), CAND_K)
+    modes, costs = K.candidates(CAND_K, mip_mode, mip_cost, intra["cost"], CAND_INTRA_BIAS, fine["cost"], CAND_ANGULAR_BIAS)
+    _freeze(modes, costs, mip_mode, mip_cost)
+    return frame, un, modes, costs, {"mip_mode": mip_mode, "mip_cost": mip_cost, "intra_cost": intra["cost"], "ang_cost": fine["cost"]}
+
+
+def family_of(modes):
+    """0 MIP, 1 Planar / DC, 2 angular, -1 none, per mode code."""
+    modes = np.asarray(modes)
+    return np.where(modes < 32, 0, np.where(modes == 0xFF, -1, np.where(modes >= 0xF0, 1, 2)))
