@@ -514,7 +514,9 @@ int mip_intra_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs
  *
  * NOT modelled: VVC's 4-tap cubic / Gaussian interpolation (the 2-tap filter above is VVC's
  * chroma filter); wide-angle remapping for non-square blocks; PDPC of modes 2..17 and 51..66;
- * reference smoothing; multi-reference lines and ISP; the real above-right / below-left samples.
+ * reference smoothing; multi-reference lines and ISP; with mip_angular_refs(MIP_ANG_REFS_EXTENDED)
+ * availability below binary / ternary splits is z-order (without it, the default, the above-right /
+ * below-left samples are the substitutes above).
  *
  * Cost.  Exactly mip_intra_device's: SAD and the engine's 4x4-Hadamard SATD of `out` against
  * F[(y+j)*W + x+i] (CUs right of the frame wrap as in the cost tables), cost = min(2*SAD, SATD).
@@ -603,6 +605,60 @@ int mip_angular_refine_device(mip_engine *e, const uint16_t *d_frames, const uin
 int mip_angular_refine_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs_or_null, int nframes,
                               const uint8_t *modes, int nmodes, int seeds,
                               int32_t *cost_out, uint8_t *ang_mode_out, int32_t *ang_cost_out, uint8_t *tried_out);
+
+/* Real above-right and below-left reference samples for the angular family (additive to ABI 7; no
+ * reference counterpart).  An engine-level switch: with MIP_ANG_REFS_EXTENDED every angular entry
+ * point of that engine -- mip_angular_device / _frames, mip_angular_refine_device / _frames, the
+ * MIP_PRED_ANGULAR items of mip_predict_device_ex / mip_predict_frames_ex, mip_predicted_frames_ex
+ * with MIP_CHAIN_ANGULAR and mip_candidates_frames with MIP_CAND_ANGULAR -- extends the two reference
+ * lines by the real samples past top[w-1] and left[h-1] where they exist and precede the CU in coding
+ * order.  The default, MIP_ANG_REFS_SUBSTITUTED, is the contract of mip_angular_device as written
+ * above, unchanged.  MIP, Planar / DC, the partition and mip_candidates_device do not look at the
+ * switch.  The setting is read when a call builds its launch: work already enqueued keeps the
+ * setting it was enqueued with, no synchronisation is needed, and the cost kernels and the block
+ * output of one engine always agree (the SAD / SATD of an emitted block are the table entries).
+ *
+ * The engine predicts from original (or filtered) samples, not from reconstructed ones, so the real
+ * samples exist whenever they lie inside the frame; only their causal order is modelled.
+ *
+ * Everything of mip_angular_device stays word for word, except the lengths of the two lines.
+ *
+ * Order key.  The key of the sample at frame position (sx, sy) is the pair (raster index of the CTU
+ * that holds it, Morton code of ((sx % 128) >> 2, (sy % 128) >> 2) with x in the even bits and y in
+ * the odd bits), compared lexicographically: z-scan order of 4x4 blocks inside CTU raster order.
+ * This is THE MODEL: it is exact for quad-tree splits and an approximation below binary / ternary
+ * splits.
+ *
+ * A CU that is unavailable, or not wholly inside the frame (x + w > W or y + h > H: the wrapped
+ * CUs), has E_top = E_left = 0.
+ *
+ * Top line of any other CU: extended by E_top, the largest n in 0..h such that every t in
+ * [w, w + n) meets all of: y > 0; x + t < W; key(x + t, y - 1) < key(x, y); with an engine filter,
+ * R[(y-1)*W + x + t] is not among the samples the filter leaves undefined (with caller references
+ * the MIP_FILTER_NONE set applies: none).  Then top[t] = R[(y-1)*W + x + t] for t in [w, w + E_top).
+ *
+ * Left line: extended by E_left, the largest n in 0..w such that every t in [h, h + n) meets all of:
+ * x > 0; y + t < H; key(x - 1, y + t) < key(x, y); the same undefined-sample condition on
+ * R[(y+t)*W + x - 1].  Then left[t] = R[(y+t)*W + x - 1] for t in [h, h + E_left).
+ *
+ * Predictor.  The main line has length M' = M + E(main) (E_top in the vertical class, E_left in the
+ * horizontal one): ref[k] = main[min(k, M') - 1] for k >= 1.  The side projection keeps its cap S:
+ * negative angles never reach past the side's end.  PDPC of modes 18 and 50, the corner, the clip,
+ * SAD / SATD / cost, the tables, the ang pair, the merge and `tried` are unchanged.
+ *
+ * Consequences: every output of modes 18..50 equals the substituted one; so does every output of a
+ * CU with E_top = E_left = 0; a CU with E_top = h predicts mode 66 as top[i + j + 1] exactly.
+ *
+ * mip_angular_refs: 0, or <0 for a NULL engine ("engine is NULL") or a value other than the two
+ * below.  mip_angular_refs_get: the current setting, <0 for NULL.
+ * mip_extended_refs (host only, like mip_unavailable_cus): per CU [nCTUs*5380] the number of real
+ * samples that extend its top line (0..h) and its left line (0..w) under the rule above, with the
+ * availability / undefined-sample set of `filter`.  Either output may be NULL, not both. */
+#define MIP_ANG_REFS_SUBSTITUTED 0   /* default: the lines of mip_angular_device */
+#define MIP_ANG_REFS_EXTENDED    1
+int mip_angular_refs(mip_engine *e, int refs);
+int mip_angular_refs_get(const mip_engine *e);
+int mip_extended_refs(int width, int height, int filter, uint8_t *top_out, uint8_t *left_out);
 
 /* The whole chain on host frames, synchronous like mip_partition_frames (it first waits for every
  * call in flight; an open merged chunk is launched): in chunks of at most max_batch frames --

@@ -165,6 +165,66 @@ MIP_INTRA_HD void ang_block(const Bound &b, const AngMode &md, int corner, int l
   else ang_block_class<false>(b, md, corner, lw, lh, i0, j0, org, sad, satd);
 }
 
+// ---- extended reference lines (include/mipgpu.h, mip_angular_refs): the real above-right and
+// below-left samples.  The order key of the sample at frame position (sx, sy): the raster index
+// of its CTU, then the Morton code of its 4x4 block inside the CTU (x the even bits, y the odd
+// ones) -- z-scan of 4x4 blocks inside CTU raster order.
+MIP_INTRA_HD uint32_t ang_spread5(uint32_t v) {  // bit k of v (k < 5) to bit 2k
+  v = (v | v << 8) & 0x00ffu;
+  v = (v | v << 4) & 0x0f0fu;
+  v = (v | v << 2) & 0x3333u;
+  return (v | v << 1) & 0x5555u;
+}
+MIP_INTRA_HD uint32_t ang_order_key(int sx, int sy, int ctu_cols) {
+  const uint32_t ctu = (uint32_t)((sy >> 7) * ctu_cols + (sx >> 7));
+  return ctu << 10 | ang_spread5((uint32_t)(sx & 127) >> 2) | ang_spread5((uint32_t)(sy & 127) >> 2) << 1;
+}
+// The two lengths of the w x h CU at (x, y): how many real samples extend its top line (0..h) and
+// its left line (0..w).  undefined(linear index): the reference sample is one an engine filter
+// leaves undefined (work_plan.h filter_poison; never, without one).
+struct AngExt {
+  int top, left;
+};
+template <class Undefined>
+inline AngExt ang_ext_lengths(int W, int H, int x, int y, int w, int h, bool unavailable, const Undefined &undefined) {
+  AngExt e{0, 0};
+  if (unavailable || x + w > W || y + h > H) return e;
+  const int cols = (W + 127) / 128;
+  const uint32_t own = ang_order_key(x, y, cols);
+  while (e.top < h && y > 0 && x + w + e.top < W && ang_order_key(x + w + e.top, y - 1, cols) < own &&
+         !undefined((long long)(y - 1) * W + x + w + e.top))
+    e.top++;
+  while (e.left < w && x > 0 && y + h + e.left < H && ang_order_key(x - 1, y + h + e.left, cols) < own &&
+         !undefined((long long)(y + h + e.left) * W + x - 1))
+    e.left++;
+  return e;
+}
+// A Bound as one class sees it with its main line extended: w (vertical class) or h (horizontal
+// class) is M' = M + E(main), the other length stays the side's cap S.  Over it ang_ref,
+// ang_ref_main, ang_sample and ang_block_class are the extended predictor: a larger clamp bound
+// for reads of the main line, nothing else.  The Bound's sample(line, t) must reach t < M'.
+template <class Bound>
+struct AngExtView {
+  const Bound &b;
+  int w, h;
+  MIP_INTRA_HD int sample(bool top_line, int t) const { return b.sample(top_line, t); }
+  MIP_INTRA_HD int corner() const { return b.corner(); }
+};
+template <class Bound>
+MIP_INTRA_HD AngExtView<Bound> ang_ext_view(const Bound &b, bool vert, int e_top, int e_left) {
+  return AngExtView<Bound>{b, b.w + (vert ? e_top : 0), b.h + (vert ? 0 : e_left)};
+}
+template <class Bound>
+MIP_INTRA_HD int ang_sample_ext(const Bound &b, int e_top, int e_left, const AngMode &md, int lw, int lh, int i, int j) {
+  return ang_sample(ang_ext_view(b, md.m >= 34, e_top, e_left), md, lw, lh, i, j);
+}
+template <class Bound>
+MIP_INTRA_HD void ang_block_ext(const Bound &b, int e_top, int e_left, const AngMode &md, int corner, int lw, int lh, int i0, int j0,
+                                const int *org, int &sad, int &satd) {
+  if (md.m >= 34) ang_block_class<true>(ang_ext_view(b, true, e_top, e_left), md, corner, lw, lh, i0, j0, org, sad, satd);
+  else ang_block_class<false>(ang_ext_view(b, false, e_top, e_left), md, corner, lw, lh, i0, j0, org, sad, satd);
+}
+
 // ---- argmin over the list (in list order, i.e. increasing mode: ties keep the lower mode) and
 // the merge: the best angular mode replaces the current decision only if its biased cost is
 // strictly lower.  Unavailable CUs (either side) stay as they are.
@@ -247,8 +307,9 @@ MIP_INTRA_HD void ang_best_step_any(uint8_t &mode, int32_t &cost, int m, int32_t
 }
 
 // ---- host side: one CU (every mode of the list), then the whole walk
+// (e_top / e_left: the CU's extended lengths, 0 / 0 the substituted lines)
 inline void angular_cu_host(const uint16_t *orig, const uint16_t *refs, int width, int x, int y, int lw, int lh, const AngList &list,
-                            int32_t *sad, int32_t *satd) {
+                            int32_t *sad, int32_t *satd, int e_top = 0, int e_left = 0) {
   const IntraHostRef ref{refs, width};
   const int w = 1 << lw, h = 1 << lh;
   const AngBound<IntraHostRef> b{ref, x, y, w, h};
@@ -261,7 +322,7 @@ inline void angular_cu_host(const uint16_t *orig, const uint16_t *refs, int widt
         for (int c = 0; c < 4; c++) org[4 * r + c] = orig[(size_t)(y + j0 + r) * width + x + i0 + c];
       for (int q = 0; q < list.n; q++) {
         int s, t;
-        ang_block(b, ang_unpack(list.packed[q]), corner, lw, lh, i0, j0, org, s, t);
+        ang_block_ext(b, e_top, e_left, ang_unpack(list.packed[q]), corner, lw, lh, i0, j0, org, s, t);
         sad[q] += s;
         satd[q] += t;
       }
@@ -269,12 +330,13 @@ inline void angular_cu_host(const uint16_t *orig, const uint16_t *refs, int widt
 }
 
 // The predicted block of one CU and mode, sample by sample (ang_sample): row r at out[r * pitch].
-inline void angular_predict_cu_host(const uint16_t *refs, int width, int x, int y, int lw, int lh, int mode, uint16_t *out, int pitch) {
+inline void angular_predict_cu_host(const uint16_t *refs, int width, int x, int y, int lw, int lh, int mode, uint16_t *out, int pitch,
+                                    int e_top = 0, int e_left = 0) {
   const IntraHostRef ref{refs, width};
   const AngBound<IntraHostRef> b{ref, x, y, 1 << lw, 1 << lh};
   const AngMode md = ang_unpack(ang_pack(mode));
   for (int j = 0; j < (1 << lh); j++)
-    for (int i = 0; i < (1 << lw); i++) out[(size_t)j * pitch + i] = (uint16_t)ang_sample(b, md, lw, lh, i, j);
+    for (int i = 0; i < (1 << lw); i++) out[(size_t)j * pitch + i] = (uint16_t)ang_sample_ext(b, e_top, e_left, md, lw, lh, i, j);
 }
 
 // Everything mip_angular_device writes, on host arrays (each output optional, the pairs given
@@ -282,10 +344,13 @@ inline void angular_predict_cu_host(const uint16_t *refs, int width, int x, int 
 // [nctus*5380] the availability set that goes with refs, modes / nmodes the call's list; cost /
 // sad / satd [nframes][nctus*5380][65], ang_mode / ang_cost and best_mode / best_cost
 // [nframes][nctus*5380].  Returns 0, or -1 for arguments the entry point rejects (nothing
-// written).
+// written).  ext_top / ext_left [nctus*5380] (both or neither): the extended lengths of
+// mip_extended_refs for the same availability set; NULL is the substituted lines.
 inline int angular_frames_host(const uint16_t *frames, const uint16_t *refs, const uint8_t *unavail, int width, int height,
                                int nframes, const uint8_t *modes, int nmodes, int32_t *cost, int32_t *sad, int32_t *satd,
-                               uint8_t *ang_mode, int32_t *ang_cost, int32_t bias, uint8_t *best_mode, int32_t *best_cost) {
+                               uint8_t *ang_mode, int32_t *ang_cost, int32_t bias, uint8_t *best_mode, int32_t *best_cost,
+                               const uint8_t *ext_top = nullptr, const uint8_t *ext_left = nullptr) {
+  if (!ext_top != !ext_left) return -1;
   if (!frames || !refs || !unavail || width <= 0 || height <= 0 || width % 4 || height % 4 || nframes < 1) return -1;
   if (!ang_mode != !ang_cost || !best_mode != !best_cost) return -1;
   if (!cost && !sad && !satd && !ang_cost && !best_cost) return -1;
@@ -305,7 +370,7 @@ inline int angular_frames_host(const uint16_t *frames, const uint16_t *refs, con
           if (on)
             angular_cu_host(frames + f * fs, refs + f * fs, width, 128 * (c % cols) + intra_axis(sd.xb, sd.xs, sd.xd, cu % sd.ncols),
                             128 * (c / cols) + intra_axis(sd.yb, sd.ys, sd.yd, cu / sd.ncols), intra_log2(sd.w), intra_log2(sd.h), list,
-                            a, b);
+                            a, b, ext_top ? ext_top[k] : 0, ext_left ? ext_left[k] : 0);
           const size_t at = (size_t)f * nctus * MIP_CUS_PER_CTU + k;
           for (int slot = 0; slot < kAngModes; slot++) {
             if (cost) cost[at * kAngModes + slot] = none;
@@ -331,12 +396,14 @@ inline int angular_frames_host(const uint16_t *frames, const uint16_t *refs, con
 }
 
 // Everything mip_angular_refine_device writes, on host arrays: angular_frames_host's arguments
-// plus seeds and the optional tried [nframes][nctus*5380].  Per available CU the list's costs, the
+// plus seeds and the optional tried [nframes][nctus*5380] (and its ext_top / ext_left).  Per available CU the list's costs, the
 // running top three, the candidate step, the candidates' costs, then the pair over both.
 inline int angular_refine_frames_host(const uint16_t *frames, const uint16_t *refs, const uint8_t *unavail, int width, int height,
                                       int nframes, const uint8_t *modes, int nmodes, int seeds, int32_t *cost, int32_t *sad,
                                       int32_t *satd, uint8_t *ang_mode, int32_t *ang_cost, uint8_t *tried, int32_t bias,
-                                      uint8_t *best_mode, int32_t *best_cost) {
+                                      uint8_t *best_mode, int32_t *best_cost, const uint8_t *ext_top = nullptr,
+                                      const uint8_t *ext_left = nullptr) {
+  if (!ext_top != !ext_left) return -1;
   if (!frames || !refs || !unavail || width <= 0 || height <= 0 || width % 4 || height % 4 || nframes < 1) return -1;
   if (!ang_mode != !ang_cost || !best_mode != !best_cost) return -1;
   if (!cost && !sad && !satd && !ang_cost && !best_cost && !tried) return -1;
@@ -367,7 +434,7 @@ inline int angular_refine_frames_host(const uint16_t *frames, const uint16_t *re
             const int lw = intra_log2(sd.w), lh = intra_log2(sd.h);
             int32_t a[kAngModes], b[kAngModes];
             auto take = [&](const AngList &l) {
-              angular_cu_host(frames + f * fs, refs + f * fs, width, x, y, lw, lh, l, a, b);
+              angular_cu_host(frames + f * fs, refs + f * fs, width, x, y, lw, lh, l, a, b, ext_top ? ext_top[k] : 0, ext_left ? ext_left[k] : 0);
               for (int q = 0; q < l.n; q++) {
                 const int m = ang_unpack(l.packed[q]).m;
                 if (cost) cost[at * kAngModes + m - 2] = intra_cost(a[q], b[q]);

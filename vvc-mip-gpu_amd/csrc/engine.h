@@ -7,6 +7,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -142,6 +143,11 @@ struct mip_engine {
   // the 16 32x32 blocks of a CTU (intra_plan.h intra_build_slots).
   uint32_t *d_intra_slots = nullptr;
   int intra_slots_per_block = 0;
+  // Extended angular reference lines (mip_angular_refs): the setting, read when a call builds its
+  // launch, and -- uploaded at the first extended call -- the lengths of mip_extended_refs per CU
+  // [nctus * 5380] as top | left << 8, [0] / [1] for the sets of d_pred_unavail [0] / [1].
+  std::atomic<int> ang_refs{MIP_ANG_REFS_SUBSTITUTED};
+  uint16_t *d_ang_ext[2] = {};
   int resident[2] = {0, 0};  // persistent search grid (workgroups resident on this device), [alt]
   int resident_wide[2] = {0, 0};  // the same for 16-wave workgroups
   int resident_four[2] = {0, 0};  // the four-wave twin's (8-wave workgroups; 0: not available)

@@ -97,6 +97,33 @@ static int ensure_pred_tables(mip_engine *e) {
   return 0;
 }
 
+// The engine's extended-line lengths (mip_engine::d_ang_ext), uploaded at the first call with
+// MIP_ANG_REFS_EXTENDED: mip_extended_refs for the two sets of d_pred_unavail.
+static int ensure_ext_tables(mip_engine *e) {
+  if (e->d_ang_ext[1]) return 0;
+  const size_t ncus = (size_t)e->nctus * MIP_CUS_PER_CTU;
+  std::vector<uint8_t> top(ncus), left(ncus);
+  std::vector<uint16_t> both(ncus);
+  for (int m = 0; m < 2; m++) {
+    if (m == 1 && e->opts.filter == MIP_FILTER_NONE) {
+      e->d_ang_ext[1] = e->d_ang_ext[0];
+      break;
+    }
+    if (!e->d_ang_ext[m]) {  // (kept from a call that failed half-way)
+      if (mip_extended_refs(e->width, e->height, m ? e->opts.filter : MIP_FILTER_NONE, top.data(), left.data()) != 0) return -1;
+      for (size_t k = 0; k < ncus; k++) both[k] = (uint16_t)(top[k] | left[k] << 8);
+      uint16_t *d = nullptr;
+      HIP_TRY(dev_malloc(e->device, (void **)&d, ncus * sizeof(uint16_t)));
+      if (hipMemcpy(d, both.data(), ncus * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess) {
+        dev_free(d);
+        return fail("uploading the extended reference lengths failed");
+      }
+      e->d_ang_ext[m] = d;
+    }
+  }
+  return 0;
+}
+
 // refs: the reference frames to predict from (already resolved); engine_refs: they are the
 // engine filter's output (its unavailable set applies).
 static int predict_launch(mip_engine *e, const uint16_t *refs, bool engine_refs, int nframes, const mip_pred_item *d_items,
@@ -120,7 +147,17 @@ static int predict_launch(mip_engine *e, const uint16_t *refs, bool engine_refs,
   HIP_TRY(mipgpu::launch_predict(a, s));
   // MIP_PRED_ANGULAR: the kernel above has rejected and counted the angular items; the angular
   // kernel emits them behind it and takes them off the count (final in stream order)
-  if (flags & MIP_PRED_ANGULAR) HIP_TRY(mipgpu::launch_predict_angular(a, s));
+  if (flags & MIP_PRED_ANGULAR) {
+    if (e->ang_refs.load() == MIP_ANG_REFS_EXTENDED) {  // (the setting of this launch)
+      if (ensure_ext_tables(e) != 0) return -1;
+      mipgpu::PredictExtArgs x{};
+      static_cast<mipgpu::PredictArgs &>(x) = a;
+      x.ext = e->d_ang_ext[engine_refs ? 1 : 0];
+      HIP_TRY(mipgpu::launch_predict_angular_ext(x, s));
+    } else {
+      HIP_TRY(mipgpu::launch_predict_angular(a, s));
+    }
+  }
   return 0;
 }
 
@@ -507,11 +544,14 @@ static int angular_device_impl(mip_engine *e, const uint16_t *d_frames, const ui
   HIP_TRY(hipSetDevice(e->device));
   if (flush_open(e) != 0) return -1;  // (device-API work orders itself after the host calls)
   if (ensure_intra_tables(e) != 0) return -1;
+  const bool extended = e->ang_refs.load() == MIP_ANG_REFS_EXTENDED;  // (the setting of this launch)
+  if (extended && ensure_ext_tables(e) != 0) return -1;
   hipStream_t s = (hipStream_t)stream;
   const uint16_t *refs = nullptr;
   bool engine_refs = false;
   if (engine_refs_begin(e, d_frames, d_refs, nframes, s, &refs, &engine_refs) != 0) return -1;
-  mipgpu::AngularRefineArgs a{};  // (the plain launch takes its AngularArgs part)
+  mipgpu::AngularExtArgs a{};  // (the substituted launches take their AngularRefineArgs / AngularArgs part)
+  a.ext = extended ? e->d_ang_ext[engine_refs ? 1 : 0] : nullptr;
   a.orig = d_frames;
   a.refs = refs;
   a.unavail = e->d_pred_unavail[engine_refs ? 1 : 0];
@@ -537,9 +577,9 @@ static int angular_device_impl(mip_engine *e, const uint16_t *d_frames, const ui
     a.tried = d_tried;
     a.nseeds = std::min(seeds, list.n);
     for (int m = MIP_ANGULAR_FIRST; m <= MIP_ANGULAR_LAST; m++) a.all[m - MIP_ANGULAR_FIRST] = mipgpu::ang_pack(m);
-    HIP_TRY(mipgpu::launch_angular_refine(a, s));
+    HIP_TRY(extended ? mipgpu::launch_angular_ext_refine(a, s) : mipgpu::launch_angular_refine(a, s));
   } else {
-    HIP_TRY(mipgpu::launch_angular(a, s));
+    HIP_TRY(extended ? mipgpu::launch_angular_ext(a, s) : mipgpu::launch_angular(a, s));
   }
   return engine_refs_end(e, engine_refs, s);
 }

@@ -1,7 +1,8 @@
 // mip_kernels.h -- launch interface between the C-ABI host code (mipgpu.cpp, host_pipeline.cpp)
 // and the gfx950 kernels (mip_search.hip, mip_decide.hip, mip_filter.hip, mip_fixup.hip,
 // mip_predict.hip, mip_predict_angular.hip, mip_partition.hip, mip_intra.hip, mip_angular.hip,
-// mip_angular_refine.hip, mip_candidates.hip).  Not part of the public ABI.
+// mip_angular_refine.hip, mip_angular_ext.hip, mip_predict_angular_ext.hip, mip_candidates.hip).
+// Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -249,6 +250,21 @@ struct AngularRefineArgs : AngularArgs {
   uint32_t all[65];           // ang_pack of every mode 2..66 (staged in LDS: a per-lane lookup)
 };
 hipError_t launch_angular_refine(const AngularRefineArgs &a, hipStream_t s);
+
+// The angular family with extended reference lines (mip_angular_refs MIP_ANG_REFS_EXTENDED):
+// angular_ext_kernel and angular_ext_refine_kernel (mip_angular_ext.hip) are angular_kernel and
+// angular_refine_kernel with the two line extensions staged and each CU's main line lengthened by
+// its entry of `ext`; angular_ext_predict_kernel (mip_predict_angular_ext.hip) is
+// angular_predict_kernel with the longer per-item line.  The launch rules are their siblings'.
+struct AngularExtArgs : AngularRefineArgs {  // (the plain launch does not look at tried, nseeds, all)
+  const uint16_t *ext;        // [nctus * 5380] E_top | E_left << 8 (mip_extended_refs, the set of unavail)
+};
+hipError_t launch_angular_ext(const AngularExtArgs &a, hipStream_t s);
+hipError_t launch_angular_ext_refine(const AngularExtArgs &a, hipStream_t s);
+struct PredictExtArgs : PredictArgs {
+  const uint16_t *ext;        // as AngularExtArgs::ext
+};
+hipError_t launch_predict_angular_ext(const PredictExtArgs &a, hipStream_t s);
 
 // K-best candidate lists over the mode families (candidates_kernel, mip_candidates.hip): one lane
 // per CU, one wave per workgroup, the CU's keys (candidates_plan.h) in one LDS row.

@@ -11,6 +11,7 @@
 #include <cstdarg>
 #include <cstring>
 
+#include "angular_plan.h"
 #include "mip_tables.h"
 
 thread_local std::string g_err;
@@ -321,6 +322,42 @@ int mip_unavailable_cus(int width, int height, int filter, uint8_t *cu_out) {
   return 0;
 }
 
+int mip_extended_refs(int width, int height, int filter, uint8_t *top_out, uint8_t *left_out) {
+  if ((!top_out && !left_out) || width <= 0 || height <= 0 || width % 4 || height % 4) return fail("bad extended-reference arguments");
+  if (filter < MIP_FILTER_NONE || filter > MIP_FILTER_2D_FLOAT_5x5) return fail("invalid filter %d", filter);
+  const mipgpu::Poison ps = mipgpu::filter_poison(width, height, filter);
+  const auto undefined = [&](long long li) { return ps.any && ps.at(li, width); };
+  const int cols = (width + 127) / 128, n = mip_num_ctus(width, height);
+  size_t k = 0;
+  for (int c = 0; c < n; c++) {
+    const int cx = 128 * (c % cols), cy = 128 * (c / cols);
+    for (int s = 0; s < MIP_NUM_SHAPES; s++) {
+      const mip_shape_desc &sd = kShapes[s];
+      for (int cu = 0; cu < sd.ncu; cu++, k++) {
+        const int x = cx + axis_pos(sd.xb, sd.xs, sd.xd, cu % sd.ncols), y = cy + axis_pos(sd.yb, sd.ys, sd.yd, cu / sd.ncols);
+        const bool off = !cu_defined(width, height, x, y, sd.w, sd.h) || mipgpu::reads_poison(ps, width, x, y, sd.w, sd.h);
+        const mipgpu::AngExt e = mipgpu::ang_ext_lengths(width, height, x, y, sd.w, sd.h, off, undefined);
+        if (top_out) top_out[k] = (uint8_t)e.top;
+        if (left_out) left_out[k] = (uint8_t)e.left;
+      }
+    }
+  }
+  return 0;
+}
+
+int mip_angular_refs(mip_engine *e, int refs) {
+  if (!e) return fail("engine is NULL");
+  if (refs != MIP_ANG_REFS_SUBSTITUTED && refs != MIP_ANG_REFS_EXTENDED) return fail("unknown angular reference setting %d", refs);
+  std::lock_guard<std::recursive_mutex> lk(e->mu);  // (a call in progress on another thread keeps one setting throughout)
+  e->ang_refs.store(refs);
+  return 0;
+}
+
+int mip_angular_refs_get(const mip_engine *e) {
+  if (!e) return fail("engine is NULL");
+  return e->ang_refs.load();
+}
+
 int mip_cu_position(int shape, int cu, int *x, int *y) {
   if (shape < 0 || shape >= MIP_NUM_SHAPES) return fail("bad shape index %d", shape);
   const mip_shape_desc &s = kShapes[shape];
@@ -354,6 +391,8 @@ int mip_engine_destroy(mip_engine *e) {
   if (e->d_pred_unavail[1] != e->d_pred_unavail[0]) dev_free(e->d_pred_unavail[1]);
   dev_free(e->d_pred_unavail[0]);
   dev_free(e->d_pred_geo);
+  if (e->d_ang_ext[1] != e->d_ang_ext[0]) dev_free(e->d_ang_ext[1]);
+  dev_free(e->d_ang_ext[0]);
   dev_free(e->d_part_leaf);
   dev_free(e->d_part_ctu);
   dev_free(e->d_intra_slots);

@@ -68,6 +68,8 @@ MODE_ANGULAR_BASE = 0x80                   # MIP_MODE_ANGULAR(m) = 0x80 + m: bes
 ANGULAR_MODES = 65                         # MIP_ANGULAR_MODES: slots of the angular tables, slot = m - 2
 ANGULAR_MAX_SEEDS = 3                      # MIP_ANGULAR_MAX_SEEDS: seeds of angular_refine are 1..3
 ANGULAR_EVEN_MODES = tuple(range(2, 67, 2))   # the 33 even modes: the usual coarse list of angular_refine
+ANG_REFS_SUBSTITUTED = 0                   # MIP_ANG_REFS_SUBSTITUTED: MipEngine.angular_refs, the default
+ANG_REFS_EXTENDED = 1                      # MIP_ANG_REFS_EXTENDED: the real above-right / below-left samples
 PRED_REGULAR = 1                           # MIP_PRED_REGULAR: flags bit of predict(..., regular=True)
 PRED_ANGULAR = 4                           # MIP_PRED_ANGULAR: flags bit of predict(..., angular=True)
 CHAIN_ANGULAR = 1                          # MIP_CHAIN_ANGULAR: flags bit of mip_predicted_frames_ex (the angular stage)
@@ -149,6 +151,9 @@ def library():
         "mip_search_device_range": (ip, [vp, vp, vp, ip, ip, ip, vp, vp, vp, vp]),
         "mip_check_input": (ip, [vp, vp]),
         "mip_unavailable_cus": (ip, [ip, ip, ip, vp]),
+        "mip_extended_refs": (ip, [ip, ip, ip, vp, vp]),
+        "mip_angular_refs": (ip, [vp, ip]),
+        "mip_angular_refs_get": (ip, [vp]),
         "mip_filter_device": (ip, [vp, vp, ip, ip, ip, ip, ip, vp]),
         "mip_copy_device": (ip, [vp, vp, ctypes.c_size_t, vp]),
         "mip_topk_device": (ip, [vp, ip, ip, ip, ip, vp, vp, vp]),
@@ -300,6 +305,21 @@ class MipEngine:
 
     def __exit__(self, *exc):
         self.close()
+
+    @property
+    def angular_refs(self) -> int:
+        """ANG_REFS_SUBSTITUTED (the default) or ANG_REFS_EXTENDED: the reference lines of every
+        angular entry point of this engine (mip_angular_refs).  A call uses the setting it finds when
+        it is made; work already enqueued keeps its own."""
+        with self._lock:
+            value = library().mip_angular_refs_get(self._h)
+            _check(min(value, 0))
+            return value
+
+    @angular_refs.setter
+    def angular_refs(self, value):
+        with self._lock:
+            _check(library().mip_angular_refs(self._h, int(value)))
 
     @property
     def costs_per_frame(self) -> int:
@@ -759,6 +779,16 @@ def unavailable_cus(width, height, filter=None) -> np.ndarray:
     return out.astype(bool)
 
 
+def extended_refs(width, height, filter=None):
+    """(top, left) uint8 per CU (reference order): how many real samples extend the CU's top line
+    (0..h) and its left line (0..w) with ANG_REFS_EXTENDED, for the availability set of an engine
+    with this filter (mip_extended_refs; host only)."""
+    n = num_ctus(width, height) * CUS_PER_CTU
+    top, left = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+    _check(library().mip_extended_refs(int(width), int(height), filter_index(filter), top.ctypes.data, left.ctypes.data))
+    return top, left
+
+
 def pred_items(width, height, frame, cu, mode, layout="packed", nframes=None):
     """Prediction list for (frame, cu, mode) triples (arrays broadcast against each other; cu
     as in the decision lists, mode as in best_mode -- 0xff = none): returns (items, out_samples)
@@ -925,6 +955,6 @@ def filter_device(frames_in, frames_out, filter, kernel_idx=0, stream=None):
     return frames_out
 
 
-__all__ = ["MODE_PLANAR", "MODE_DC", "INTRA_MAX_BIAS", "MODE_ANGULAR_BASE", "ANGULAR_MODES", "ANGULAR_MAX_SEEDS", "ANGULAR_EVEN_MODES", "PRED_REGULAR", "PRED_ANGULAR", "CHAIN_ANGULAR", "PRED_ITEM", "PRED_NONE", "pred_items", "PART_MAX_LEAVES", "PART_MAX_PENALTY", "partition_device", "MipEngine", "MipError", "build_id", "source_id", "FILTERS", "FILTER_NONE", "filter_index", "filter_device", "topk_device", "library",
+__all__ = ["MODE_PLANAR", "MODE_DC", "INTRA_MAX_BIAS", "MODE_ANGULAR_BASE", "ANGULAR_MODES", "ANGULAR_MAX_SEEDS", "ANGULAR_EVEN_MODES", "ANG_REFS_SUBSTITUTED", "ANG_REFS_EXTENDED", "extended_refs", "PRED_REGULAR", "PRED_ANGULAR", "CHAIN_ANGULAR", "PRED_ITEM", "PRED_NONE", "pred_items", "PART_MAX_LEAVES", "PART_MAX_PENALTY", "partition_device", "MipEngine", "MipError", "build_id", "source_id", "FILTERS", "FILTER_NONE", "filter_index", "filter_device", "topk_device", "library",
            "pinned_empty", "unavailable_cus", "numa_node", "bind_thread", "device_cache", "copy_device",
            "layout", "SHAPES", "COSTS_PER_CTU", "CUS_PER_CTU", "UNAVAILABLE", "num_ctus"]
