@@ -512,11 +512,13 @@ int mip_intra_frames(mip_engine *e, const uint16_t *frames, const uint16_t *refs
  * For every mode out = clip(0, 1023, P or P'), in 32-bit arithmetic throughout (engine-filtered
  * references can exceed 10 bits).
  *
- * NOT modelled: VVC's 4-tap cubic / Gaussian interpolation (the 2-tap filter above is VVC's
- * chroma filter); wide-angle remapping for non-square blocks; PDPC of modes 2..17 and 51..66;
- * reference smoothing; multi-reference lines and ISP; with mip_angular_refs(MIP_ANG_REFS_EXTENDED)
- * availability below binary / ternary splits is z-order (without it, the default, the above-right /
- * below-left samples are the substitutes above).
+ * NOT modelled: wide-angle remapping for non-square blocks; PDPC of modes 2..17 and 51..66;
+ * multi-reference lines and ISP; with mip_angular_refs(MIP_ANG_REFS_EXTENDED) availability below
+ * binary / ternary splits is z-order (without it, the default, the above-right / below-left samples
+ * are the substitutes above).  The 2-tap filter above is VVC's chroma filter and the default;
+ * mip_angular_interp(MIP_ANG_INTERP_4TAP) replaces it by VVC's luma filters, with one difference:
+ * VVC leaves the last sample of its 2M-long line unsmoothed, here the [1 2 1] smoothing of the
+ * integer-slope modes runs over this engine's line with its clamp.
  *
  * Cost.  Exactly mip_intra_device's: SAD and the engine's 4x4-Hadamard SATD of `out` against
  * F[(y+j)*W + x+i] (CUs right of the frame wrap as in the cost tables), cost = min(2*SAD, SATD).
@@ -659,6 +661,62 @@ int mip_angular_refine_frames(mip_engine *e, const uint16_t *frames, const uint1
 int mip_angular_refs(mip_engine *e, int refs);
 int mip_angular_refs_get(const mip_engine *e);
 int mip_extended_refs(int width, int height, int filter, uint8_t *top_out, uint8_t *left_out);
+
+/* VVC's 4-tap cubic / Gaussian luma interpolation for the angular family (additive to ABI 7; no
+ * reference counterpart).  An engine-level switch in the shape of mip_angular_refs: with
+ * MIP_ANG_INTERP_4TAP every angular entry point of that engine -- the list of mip_angular_refs above
+ * -- predicts with VVC's luma filters.  The default, MIP_ANG_INTERP_2TAP, is the predictor of
+ * mip_angular_device as written above, unchanged.  MIP, Planar / DC, the partition and
+ * mip_candidates_device do not look at the switch.  The setting is read when a call builds its
+ * launch, next to the mip_angular_refs setting and under the same rules: work already enqueued keeps
+ * the setting it was enqueued with, and the cost kernels and the block output of one engine always
+ * agree.  The two switches are independent: all four combinations are defined.
+ *
+ * Everything of mip_angular_device and of mip_angular_refs stays word for word, except the line
+ * P = ... of the predictor: the reference source, the corner, ref[k] with its clamps, the extended
+ * length M' under MIP_ANG_REFS_EXTENDED, the side projection and its cap S, PDPC of modes 18 and 50,
+ * the clip, SAD / SATD / cost, the tables, the ang pair, the merge, `tried`, the list and bias rules.
+ *
+ * With MIP_ANG_INTERP_4TAP, for sample (i, j) of a CU with w = 1 << lw, h = 1 << lh and mode m, take
+ * d, idx, f and k = a + idx + 1 as above:
+ *     G = min(|m - 50|, |m - 18|) > T[(lw + lh) >> 1],   T[0..6] = {24, 24, 24, 14, 2, 0, 0}
+ *     c = G ? fG[f] : fC[f]
+ *     P = (c[0]*ref[k-1] + c[1]*ref[k] + c[2]*ref[k+1] + c[3]*ref[k+2] + 32) >> 6
+ * The sum can be negative: the shift is arithmetic and the arithmetic 32-bit throughout.  The same
+ * expression applies for every f, f = 0 included.  ref[] is the class's reference exactly as the
+ * engine's mip_angular_refs setting resolves it (ref[k] = main[min(k, M') - 1] for k >= 1, the side
+ * projection for k < 0); ref[0] is the corner, also for A >= 0, where the 2-tap predictor never
+ * reads it.
+ *
+ * fG[f] = {16 - (f>>1), 32 - (f>>1), 16 + (f>>1), f>>1}; fG[0] = {16, 32, 16, 0} is VVC's [1 2 1]
+ * reference smoothing of the integer-slope modes.  fC[f] for f = 0..16:
+ *     { 0,64, 0, 0} {-1,63, 2, 0} {-2,62, 4, 0} {-2,60, 7,-1} {-2,58,10,-2} {-3,57,12,-2}
+ *     {-4,56,14,-2} {-4,55,15,-2} {-4,54,16,-2} {-5,53,18,-2} {-6,52,20,-2} {-6,49,24,-3}
+ *     {-6,46,28,-4} {-5,44,29,-4} {-4,42,30,-4} {-4,39,33,-4} {-4,36,36,-4}
+ * and fC[32 - f] is fC[f] reversed.  fC[0] is the identity; every row of both tables sums to 64.
+ * (VVC's intra luma filters and its intraHorVerDistThres; these tables are the contract.)
+ *
+ * Consequences: modes 18 and 50 equal the 2-tap outputs everywhere (f = 0 and G is false: the
+ * identity); modes 2, 34 and 66 equal the 2-tap outputs on CUs with (lw + lh) >> 1 == 2 (4x4, 4x8,
+ * 8x4; on every larger CU they are smoothed by fG[0]); a constant reference line predicts that
+ * constant in every mode; a line that is v everywhere but v + 64 at one sample predicts v + c at the
+ * samples whose window covers it, c the coefficient of the tap that lands on it (v in 6 .. 959: no
+ * clip).
+ * With MIP_ANG_REFS_EXTENDED the tap k+2 of a negative-angle mode reaches ref[M+1], the first sample
+ * of the extension, so of the consequences listed under mip_angular_refs "modes 18..50 equal the
+ * substituted outputs" holds for modes 18 and 50 only; a CU with E_top = E_left = 0 still equals its
+ * substituted outputs in every mode.
+ *
+ * mip_angular_interp: 0, or <0 for a NULL engine ("engine is NULL") or a value other than the two
+ * below.  mip_angular_interp_get: the current setting, <0 for NULL.
+ * mip_angular_filter (host only): which table a w x h = (1 << lw) x (1 << lh) CU takes for `mode`
+ * under MIP_ANG_INTERP_4TAP -- 0 the cubic fC, 1 the Gaussian fG (G above); <0 for lw or lh outside
+ * 2..6 or a mode outside 2..66. */
+#define MIP_ANG_INTERP_2TAP 0   /* default: the predictor of mip_angular_device as written */
+#define MIP_ANG_INTERP_4TAP 1
+int mip_angular_interp(mip_engine *e, int interp);
+int mip_angular_interp_get(const mip_engine *e);
+int mip_angular_filter(int lw, int lh, int mode);
 
 /* The whole chain on host frames, synchronous like mip_partition_frames (it first waits for every
  * call in flight; an open merged chunk is launched): in chunks of at most max_batch frames --

@@ -225,6 +225,122 @@ MIP_INTRA_HD void ang_block_ext(const Bound &b, int e_top, int e_left, const Ang
   else ang_block_class<false>(ang_ext_view(b, false, e_top, e_left), md, corner, lw, lh, i0, j0, org, sad, satd);
 }
 
+// ---- VVC's 4-tap luma interpolation (include/mipgpu.h, mip_angular_interp, MIP_ANG_INTERP_4TAP):
+// only the line P = ... of the predictor changes.  The cubic table fC for f = 0..16 (fC[32 - f] is
+// fC[f] reversed), the Gaussian fG[f] = {16 - (f>>1), 32 - (f>>1), 16 + (f>>1), f>>1}, and which of
+// the two a (CU shape, mode) takes.
+MIP_INTRA_HD int ang_cubic(int f, int t) {  // fC[f][t], f in 0..31, t in 0..3
+  constexpr signed char c[17][4] = {{0, 64, 0, 0},   {-1, 63, 2, 0},  {-2, 62, 4, 0},   {-2, 60, 7, -1},  {-2, 58, 10, -2}, {-3, 57, 12, -2},
+                                    {-4, 56, 14, -2}, {-4, 55, 15, -2}, {-4, 54, 16, -2}, {-5, 53, 18, -2}, {-6, 52, 20, -2}, {-6, 49, 24, -3},
+                                    {-6, 46, 28, -4}, {-5, 44, 29, -4}, {-4, 42, 30, -4}, {-4, 39, 33, -4}, {-4, 36, 36, -4}};
+  return f <= 16 ? c[f][t] : c[32 - f][3 - t];
+}
+MIP_INTRA_HD int ang_gauss(int f, int t) {  // fG[f][t]
+  const int h = f >> 1;
+  return t == 0 ? 16 - h : t == 1 ? 32 - h : t == 2 ? 16 + h : h;
+}
+// G of the contract: the Gaussian filter where the mode's distance from the nearer pure mode
+// exceeds the threshold of the CU's size class (lw + lh) >> 1 = 2..6.
+MIP_INTRA_HD int ang_gauss_threshold(int lw, int lh) {
+  const int n = (lw + lh) >> 1;
+  return n <= 2 ? 24 : n == 3 ? 14 : n == 4 ? 2 : 0;
+}
+MIP_INTRA_HD bool ang_filter_gauss(int m, int lw, int lh) {
+  const int dv = m > 50 ? m - 50 : 50 - m, dh = m > 18 ? m - 18 : 18 - m;
+  return (dv < dh ? dv : dh) > ang_gauss_threshold(lw, lh);
+}
+// The four coefficients of (G, f) as one word of signed bytes, c[0] lowest: every coefficient of
+// both tables lies in -6 .. 64.  The kernels keep the 64 words in LDS at index G << 5 | f.
+constexpr int kAngCoefWords = 64;
+MIP_INTRA_HD uint32_t ang_coef_word(bool gauss, int f) {
+  uint32_t w = 0;
+  for (int t = 0; t < 4; t++) w |= (uint32_t)((gauss ? ang_gauss(f, t) : ang_cubic(f, t)) & 0xff) << (8 * t);
+  return w;
+}
+MIP_INTRA_HD int ang_coef(uint32_t word, int t) { return (int)(word << (24 - 8 * t)) >> 24; }
+// A "Coef" is any callable coef(gauss, f) -> that word: AngCoefTable computes it; the kernels
+// have their own over the staged words.
+struct AngCoefTable {
+  MIP_INTRA_HD uint32_t operator()(bool gauss, int f) const { return ang_coef_word(gauss, f); }
+};
+// ref[k] for A >= 0 under the 4-tap filter, whose first tap reaches k = 0: the corner.
+template <bool VERT, class Bound>
+MIP_INTRA_HD int ang_ref_main0(const Bound &b, int k, int corner) {
+  const int M = VERT ? b.w : b.h;
+  const int v = b.sample(VERT, (k < 1 ? 1 : k < M ? k : M) - 1);
+  return k < 1 ? corner : v;
+}
+MIP_INTRA_HD int ang_tap4(uint32_t word, int r0, int r1, int r2, int r3) {
+  return (ang_coef(word, 0) * r0 + ang_coef(word, 1) * r1 + ang_coef(word, 2) * r2 + ang_coef(word, 3) * r3 + 32) >> 6;
+}
+// ang_sample with the 4-tap line: the taps are ref[k-1 .. k+2] (ang_ref gives the corner at 0 for
+// every angle), for every f including 0.
+template <class Bound>
+MIP_INTRA_HD int ang_sample_tap4(const Bound &b, const AngMode &md, int lw, int lh, int i, int j) {
+  const bool vert = md.m >= 34;
+  const int a = vert ? i : j, bb = vert ? j : i;
+  const int d = (bb + 1) * md.angle, idx = d >> 5, f = d & 31, c = b.corner(), k = a + idx + 1;
+  int r[4];
+  for (int t = 0; t < 4; t++) r[t] = vert ? ang_ref<true>(b, k - 1 + t, md.inv, c) : ang_ref<false>(b, k - 1 + t, md.inv, c);
+  int p = ang_tap4(ang_coef_word(ang_filter_gauss(md.m, lw, lh), f), r[0], r[1], r[2], r[3]);
+  if (md.m == 18 || md.m == 50) {
+    const int wgt = intra_pdpc_weight(a, (lw + lh - 2) >> 2);
+    const int side = b.sample(!vert, bb) - c + p;
+    p = (side * wgt + (64 - wgt) * p + 32) >> 6;
+  }
+  return ang_clip(p);
+}
+// ang_block_class with the 4-tap line: the four samples of a line along the side direction need the
+// seven consecutive ref[a0+idx .. a0+idx+6]; one coefficient word per line.
+template <bool VERT, class Bound, class Coef>
+MIP_INTRA_HD void ang_block_tap4_class(const Bound &b, const AngMode &md, int corner, int lw, int lh, int i0, int j0, const int *org,
+                                       const Coef &coef, int &sad, int &satd) {
+  const int a0 = VERT ? i0 : j0, b0 = VERT ? j0 : i0;
+  const bool pdpc = md.m == 18 || md.m == 50;
+  const bool gauss = ang_filter_gauss(md.m, lw, lh);
+  const int scale = (lw + lh - 2) >> 2;
+  int wgt[4] = {0, 0, 0, 0};
+  if (pdpc) {
+    MIP_INTRA_UNROLL
+    for (int c = 0; c < 4; c++) wgt[c] = intra_pdpc_weight(a0 + c, scale);
+  }
+  int d[16];
+  MIP_INTRA_UNROLL
+  for (int r = 0; r < 4; r++) {
+    const int dd = (b0 + r + 1) * md.angle, idx = dd >> 5, f = dd & 31;
+    const uint32_t word = coef(gauss, f);
+    int s[7];
+    if (md.angle >= 0) {
+      s[0] = ang_ref_main0<VERT>(b, a0 + idx, corner);
+      MIP_INTRA_UNROLL
+      for (int t = 1; t < 7; t++) s[t] = ang_ref_main<VERT>(b, a0 + idx + t);
+    } else {
+      MIP_INTRA_UNROLL
+      for (int t = 0; t < 7; t++) s[t] = ang_ref<VERT>(b, a0 + idx + t, md.inv, corner);
+    }
+    const int side = pdpc ? b.sample(!VERT, b0 + r) - corner : 0;
+    MIP_INTRA_UNROLL
+    for (int c = 0; c < 4; c++) {
+      int p = ang_tap4(word, s[c], s[c + 1], s[c + 2], s[c + 3]);
+      if (pdpc) p = ((side + p) * wgt[c] + (64 - wgt[c]) * p + 32) >> 6;
+      const int at = VERT ? 4 * r + c : 4 * c + r;
+      d[at] = org[at] - ang_clip(p);
+    }
+  }
+  sad = intra_sad16(d);
+  satd = intra_satd4x4(d);
+}
+template <class Bound>
+MIP_INTRA_HD int ang_sample_tap4_ext(const Bound &b, int e_top, int e_left, const AngMode &md, int lw, int lh, int i, int j) {
+  return ang_sample_tap4(ang_ext_view(b, md.m >= 34, e_top, e_left), md, lw, lh, i, j);
+}
+template <class Bound, class Coef>
+MIP_INTRA_HD void ang_block_tap4_ext(const Bound &b, int e_top, int e_left, const AngMode &md, int corner, int lw, int lh, int i0, int j0,
+                                     const int *org, const Coef &coef, int &sad, int &satd) {
+  if (md.m >= 34) ang_block_tap4_class<true>(ang_ext_view(b, true, e_top, e_left), md, corner, lw, lh, i0, j0, org, coef, sad, satd);
+  else ang_block_tap4_class<false>(ang_ext_view(b, false, e_top, e_left), md, corner, lw, lh, i0, j0, org, coef, sad, satd);
+}
+
 // ---- argmin over the list (in list order, i.e. increasing mode: ties keep the lower mode) and
 // the merge: the best angular mode replaces the current decision only if its biased cost is
 // strictly lower.  Unavailable CUs (either side) stay as they are.
@@ -307,9 +423,10 @@ MIP_INTRA_HD void ang_best_step_any(uint8_t &mode, int32_t &cost, int m, int32_t
 }
 
 // ---- host side: one CU (every mode of the list), then the whole walk
-// (e_top / e_left: the CU's extended lengths, 0 / 0 the substituted lines)
+// (e_top / e_left: the CU's extended lengths, 0 / 0 the substituted lines; interp: the engine's
+// mip_angular_interp setting, MIP_ANG_INTERP_2TAP or MIP_ANG_INTERP_4TAP)
 inline void angular_cu_host(const uint16_t *orig, const uint16_t *refs, int width, int x, int y, int lw, int lh, const AngList &list,
-                            int32_t *sad, int32_t *satd, int e_top = 0, int e_left = 0) {
+                            int32_t *sad, int32_t *satd, int e_top = 0, int e_left = 0, int interp = MIP_ANG_INTERP_2TAP) {
   const IntraHostRef ref{refs, width};
   const int w = 1 << lw, h = 1 << lh;
   const AngBound<IntraHostRef> b{ref, x, y, w, h};
@@ -322,21 +439,27 @@ inline void angular_cu_host(const uint16_t *orig, const uint16_t *refs, int widt
         for (int c = 0; c < 4; c++) org[4 * r + c] = orig[(size_t)(y + j0 + r) * width + x + i0 + c];
       for (int q = 0; q < list.n; q++) {
         int s, t;
-        ang_block_ext(b, e_top, e_left, ang_unpack(list.packed[q]), corner, lw, lh, i0, j0, org, s, t);
+        if (interp == MIP_ANG_INTERP_4TAP)
+          ang_block_tap4_ext(b, e_top, e_left, ang_unpack(list.packed[q]), corner, lw, lh, i0, j0, org, AngCoefTable{}, s, t);
+        else
+          ang_block_ext(b, e_top, e_left, ang_unpack(list.packed[q]), corner, lw, lh, i0, j0, org, s, t);
         sad[q] += s;
         satd[q] += t;
       }
     }
 }
 
-// The predicted block of one CU and mode, sample by sample (ang_sample): row r at out[r * pitch].
+// The predicted block of one CU and mode, sample by sample (ang_sample, or ang_sample_tap4 with
+// interp == MIP_ANG_INTERP_4TAP): row r at out[r * pitch].
 inline void angular_predict_cu_host(const uint16_t *refs, int width, int x, int y, int lw, int lh, int mode, uint16_t *out, int pitch,
-                                    int e_top = 0, int e_left = 0) {
+                                    int e_top = 0, int e_left = 0, int interp = MIP_ANG_INTERP_2TAP) {
   const IntraHostRef ref{refs, width};
   const AngBound<IntraHostRef> b{ref, x, y, 1 << lw, 1 << lh};
   const AngMode md = ang_unpack(ang_pack(mode));
   for (int j = 0; j < (1 << lh); j++)
-    for (int i = 0; i < (1 << lw); i++) out[(size_t)j * pitch + i] = (uint16_t)ang_sample_ext(b, e_top, e_left, md, lw, lh, i, j);
+    for (int i = 0; i < (1 << lw); i++)
+      out[(size_t)j * pitch + i] = (uint16_t)(interp == MIP_ANG_INTERP_4TAP ? ang_sample_tap4_ext(b, e_top, e_left, md, lw, lh, i, j)
+                                                                            : ang_sample_ext(b, e_top, e_left, md, lw, lh, i, j));
 }
 
 // Everything mip_angular_device writes, on host arrays (each output optional, the pairs given
@@ -345,12 +468,13 @@ inline void angular_predict_cu_host(const uint16_t *refs, int width, int x, int 
 // sad / satd [nframes][nctus*5380][65], ang_mode / ang_cost and best_mode / best_cost
 // [nframes][nctus*5380].  Returns 0, or -1 for arguments the entry point rejects (nothing
 // written).  ext_top / ext_left [nctus*5380] (both or neither): the extended lengths of
-// mip_extended_refs for the same availability set; NULL is the substituted lines.
+// mip_extended_refs for the same availability set; NULL is the substituted lines.  interp: the
+// mip_angular_interp setting (anything but the two values is rejected).
 inline int angular_frames_host(const uint16_t *frames, const uint16_t *refs, const uint8_t *unavail, int width, int height,
                                int nframes, const uint8_t *modes, int nmodes, int32_t *cost, int32_t *sad, int32_t *satd,
                                uint8_t *ang_mode, int32_t *ang_cost, int32_t bias, uint8_t *best_mode, int32_t *best_cost,
-                               const uint8_t *ext_top = nullptr, const uint8_t *ext_left = nullptr) {
-  if (!ext_top != !ext_left) return -1;
+                               const uint8_t *ext_top = nullptr, const uint8_t *ext_left = nullptr, int interp = MIP_ANG_INTERP_2TAP) {
+  if (!ext_top != !ext_left || (interp != MIP_ANG_INTERP_2TAP && interp != MIP_ANG_INTERP_4TAP)) return -1;
   if (!frames || !refs || !unavail || width <= 0 || height <= 0 || width % 4 || height % 4 || nframes < 1) return -1;
   if (!ang_mode != !ang_cost || !best_mode != !best_cost) return -1;
   if (!cost && !sad && !satd && !ang_cost && !best_cost) return -1;
@@ -370,7 +494,7 @@ inline int angular_frames_host(const uint16_t *frames, const uint16_t *refs, con
           if (on)
             angular_cu_host(frames + f * fs, refs + f * fs, width, 128 * (c % cols) + intra_axis(sd.xb, sd.xs, sd.xd, cu % sd.ncols),
                             128 * (c / cols) + intra_axis(sd.yb, sd.ys, sd.yd, cu / sd.ncols), intra_log2(sd.w), intra_log2(sd.h), list,
-                            a, b, ext_top ? ext_top[k] : 0, ext_left ? ext_left[k] : 0);
+                            a, b, ext_top ? ext_top[k] : 0, ext_left ? ext_left[k] : 0, interp);
           const size_t at = (size_t)f * nctus * MIP_CUS_PER_CTU + k;
           for (int slot = 0; slot < kAngModes; slot++) {
             if (cost) cost[at * kAngModes + slot] = none;
@@ -402,8 +526,8 @@ inline int angular_refine_frames_host(const uint16_t *frames, const uint16_t *re
                                       int nframes, const uint8_t *modes, int nmodes, int seeds, int32_t *cost, int32_t *sad,
                                       int32_t *satd, uint8_t *ang_mode, int32_t *ang_cost, uint8_t *tried, int32_t bias,
                                       uint8_t *best_mode, int32_t *best_cost, const uint8_t *ext_top = nullptr,
-                                      const uint8_t *ext_left = nullptr) {
-  if (!ext_top != !ext_left) return -1;
+                                      const uint8_t *ext_left = nullptr, int interp = MIP_ANG_INTERP_2TAP) {
+  if (!ext_top != !ext_left || (interp != MIP_ANG_INTERP_2TAP && interp != MIP_ANG_INTERP_4TAP)) return -1;
   if (!frames || !refs || !unavail || width <= 0 || height <= 0 || width % 4 || height % 4 || nframes < 1) return -1;
   if (!ang_mode != !ang_cost || !best_mode != !best_cost) return -1;
   if (!cost && !sad && !satd && !ang_cost && !best_cost && !tried) return -1;
@@ -434,7 +558,7 @@ inline int angular_refine_frames_host(const uint16_t *frames, const uint16_t *re
             const int lw = intra_log2(sd.w), lh = intra_log2(sd.h);
             int32_t a[kAngModes], b[kAngModes];
             auto take = [&](const AngList &l) {
-              angular_cu_host(frames + f * fs, refs + f * fs, width, x, y, lw, lh, l, a, b, ext_top ? ext_top[k] : 0, ext_left ? ext_left[k] : 0);
+              angular_cu_host(frames + f * fs, refs + f * fs, width, x, y, lw, lh, l, a, b, ext_top ? ext_top[k] : 0, ext_left ? ext_left[k] : 0, interp);
               for (int q = 0; q < l.n; q++) {
                 const int m = ang_unpack(l.packed[q]).m;
                 if (cost) cost[at * kAngModes + m - 2] = intra_cost(a[q], b[q]);

@@ -148,6 +148,9 @@ struct mip_engine {
   // [nctus * 5380] as top | left << 8, [0] / [1] for the sets of d_pred_unavail [0] / [1].
   std::atomic<int> ang_refs{MIP_ANG_REFS_SUBSTITUTED};
   uint16_t *d_ang_ext[2] = {};
+  // The angular interpolation filter (mip_angular_interp): the setting, read when a call builds its
+  // launch, like ang_refs.
+  std::atomic<int> ang_interp{MIP_ANG_INTERP_2TAP};
   int resident[2] = {0, 0};  // persistent search grid (workgroups resident on this device), [alt]
   int resident_wide[2] = {0, 0};  // the same for 16-wave workgroups
   int resident_four[2] = {0, 0};  // the four-wave twin's (8-wave workgroups; 0: not available)

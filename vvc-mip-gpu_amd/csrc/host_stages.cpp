@@ -124,6 +124,11 @@ static int ensure_ext_tables(mip_engine *e) {
   return 0;
 }
 
+// The 64 coefficient words of the 4-tap kernels (mip_kernels.h AngularTap4Args::coef).
+static void tap4_coefficients(uint32_t (&coef)[mipgpu::kAngCoefWords]) {
+  for (int k = 0; k < mipgpu::kAngCoefWords; k++) coef[k] = mipgpu::ang_coef_word(k >> 5, k & 31);
+}
+
 // refs: the reference frames to predict from (already resolved); engine_refs: they are the
 // engine filter's output (its unavailable set applies).
 static int predict_launch(mip_engine *e, const uint16_t *refs, bool engine_refs, int nframes, const mip_pred_item *d_items,
@@ -148,8 +153,16 @@ static int predict_launch(mip_engine *e, const uint16_t *refs, bool engine_refs,
   // MIP_PRED_ANGULAR: the kernel above has rejected and counted the angular items; the angular
   // kernel emits them behind it and takes them off the count (final in stream order)
   if (flags & MIP_PRED_ANGULAR) {
-    if (e->ang_refs.load() == MIP_ANG_REFS_EXTENDED) {  // (the setting of this launch)
-      if (ensure_ext_tables(e) != 0) return -1;
+    const bool extended = e->ang_refs.load() == MIP_ANG_REFS_EXTENDED;       // (the two settings of this launch)
+    const bool tap4 = e->ang_interp.load() == MIP_ANG_INTERP_4TAP;
+    if (extended && ensure_ext_tables(e) != 0) return -1;
+    if (tap4) {  // one kernel for both reference settings: no table is the substituted lines
+      mipgpu::PredictTap4Args x{};
+      static_cast<mipgpu::PredictArgs &>(x) = a;
+      x.ext = extended ? e->d_ang_ext[engine_refs ? 1 : 0] : nullptr;
+      tap4_coefficients(x.coef);
+      HIP_TRY(mipgpu::launch_predict_angular_tap4(x, s));
+    } else if (extended) {
       mipgpu::PredictExtArgs x{};
       static_cast<mipgpu::PredictArgs &>(x) = a;
       x.ext = e->d_ang_ext[engine_refs ? 1 : 0];
@@ -544,13 +557,15 @@ static int angular_device_impl(mip_engine *e, const uint16_t *d_frames, const ui
   HIP_TRY(hipSetDevice(e->device));
   if (flush_open(e) != 0) return -1;  // (device-API work orders itself after the host calls)
   if (ensure_intra_tables(e) != 0) return -1;
-  const bool extended = e->ang_refs.load() == MIP_ANG_REFS_EXTENDED;  // (the setting of this launch)
+  const bool extended = e->ang_refs.load() == MIP_ANG_REFS_EXTENDED;  // (the two settings of this launch)
+  const bool tap4 = e->ang_interp.load() == MIP_ANG_INTERP_4TAP;
   if (extended && ensure_ext_tables(e) != 0) return -1;
   hipStream_t s = (hipStream_t)stream;
   const uint16_t *refs = nullptr;
   bool engine_refs = false;
   if (engine_refs_begin(e, d_frames, d_refs, nframes, s, &refs, &engine_refs) != 0) return -1;
-  mipgpu::AngularExtArgs a{};  // (the substituted launches take their AngularRefineArgs / AngularArgs part)
+  mipgpu::AngularTap4Args a{};  // (the 2-tap launches take their AngularExtArgs / AngularRefineArgs / AngularArgs part)
+  if (tap4) tap4_coefficients(a.coef);  // (one 4-tap kernel per role: no table is the substituted lines)
   a.ext = extended ? e->d_ang_ext[engine_refs ? 1 : 0] : nullptr;
   a.orig = d_frames;
   a.refs = refs;
@@ -577,9 +592,10 @@ static int angular_device_impl(mip_engine *e, const uint16_t *d_frames, const ui
     a.tried = d_tried;
     a.nseeds = std::min(seeds, list.n);
     for (int m = MIP_ANGULAR_FIRST; m <= MIP_ANGULAR_LAST; m++) a.all[m - MIP_ANGULAR_FIRST] = mipgpu::ang_pack(m);
-    HIP_TRY(extended ? mipgpu::launch_angular_ext_refine(a, s) : mipgpu::launch_angular_refine(a, s));
+    HIP_TRY(tap4 ? mipgpu::launch_angular_tap4_refine(a, s)
+                 : extended ? mipgpu::launch_angular_ext_refine(a, s) : mipgpu::launch_angular_refine(a, s));
   } else {
-    HIP_TRY(extended ? mipgpu::launch_angular_ext(a, s) : mipgpu::launch_angular(a, s));
+    HIP_TRY(tap4 ? mipgpu::launch_angular_tap4(a, s) : extended ? mipgpu::launch_angular_ext(a, s) : mipgpu::launch_angular(a, s));
   }
   return engine_refs_end(e, engine_refs, s);
 }

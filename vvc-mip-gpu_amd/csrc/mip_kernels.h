@@ -266,6 +266,22 @@ struct PredictExtArgs : PredictArgs {
 };
 hipError_t launch_predict_angular_ext(const PredictExtArgs &a, hipStream_t s);
 
+// The angular family with VVC's 4-tap luma interpolation (mip_angular_interp MIP_ANG_INTERP_4TAP):
+// angular_tap4_kernel and angular_tap4_refine_kernel (mip_angular_tap4.hip) are the two _ext cost
+// kernels and angular_tap4_predict_kernel (mip_predict_angular_tap4.hip) the _ext block output,
+// with the line P = ... of the predictor replaced.  One kernel per role serves both
+// mip_angular_refs settings: ext == NULL is MIP_ANG_REFS_SUBSTITUTED (every length 0).  The launch
+// rules are their siblings'.
+struct AngularTap4Args : AngularExtArgs {  // (ext may be NULL)
+  uint32_t coef[64];          // angular_plan.h ang_coef_word at G << 5 | f (staged in LDS: a per-lane lookup)
+};
+hipError_t launch_angular_tap4(const AngularTap4Args &a, hipStream_t s);
+hipError_t launch_angular_tap4_refine(const AngularTap4Args &a, hipStream_t s);
+struct PredictTap4Args : PredictExtArgs {  // (ext may be NULL)
+  uint32_t coef[64];          // as AngularTap4Args::coef
+};
+hipError_t launch_predict_angular_tap4(const PredictTap4Args &a, hipStream_t s);
+
 // K-best candidate lists over the mode families (candidates_kernel, mip_candidates.hip): one lane
 // per CU, one wave per workgroup, the CU's keys (candidates_plan.h) in one LDS row.
 struct CandidatesArgs {

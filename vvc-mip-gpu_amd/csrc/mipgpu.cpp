@@ -358,6 +358,25 @@ int mip_angular_refs_get(const mip_engine *e) {
   return e->ang_refs.load();
 }
 
+int mip_angular_interp(mip_engine *e, int interp) {
+  if (!e) return fail("engine is NULL");
+  if (interp != MIP_ANG_INTERP_2TAP && interp != MIP_ANG_INTERP_4TAP) return fail("unknown angular interpolation setting %d", interp);
+  std::lock_guard<std::recursive_mutex> lk(e->mu);  // (a call in progress on another thread keeps one setting throughout)
+  e->ang_interp.store(interp);
+  return 0;
+}
+
+int mip_angular_interp_get(const mip_engine *e) {
+  if (!e) return fail("engine is NULL");
+  return e->ang_interp.load();
+}
+
+int mip_angular_filter(int lw, int lh, int mode) {
+  if (lw < 2 || lw > 6 || lh < 2 || lh > 6 || mode < MIP_ANGULAR_FIRST || mode > MIP_ANGULAR_LAST)
+    return fail("angular filter: lw and lh are 2..6, the mode %d..%d", MIP_ANGULAR_FIRST, MIP_ANGULAR_LAST);
+  return mipgpu::ang_filter_gauss(mode, lw, lh) ? 1 : 0;
+}
+
 int mip_cu_position(int shape, int cu, int *x, int *y) {
   if (shape < 0 || shape >= MIP_NUM_SHAPES) return fail("bad shape index %d", shape);
   const mip_shape_desc &s = kShapes[shape];

@@ -70,6 +70,8 @@ ANGULAR_MAX_SEEDS = 3                      # MIP_ANGULAR_MAX_SEEDS: seeds of ang
 ANGULAR_EVEN_MODES = tuple(range(2, 67, 2))   # the 33 even modes: the usual coarse list of angular_refine
 ANG_REFS_SUBSTITUTED = 0                   # MIP_ANG_REFS_SUBSTITUTED: MipEngine.angular_refs, the default
 ANG_REFS_EXTENDED = 1                      # MIP_ANG_REFS_EXTENDED: the real above-right / below-left samples
+ANG_INTERP_2TAP = 0                        # MIP_ANG_INTERP_2TAP: MipEngine.angular_interp, the default
+ANG_INTERP_4TAP = 1                        # MIP_ANG_INTERP_4TAP: VVC's cubic / Gaussian luma interpolation
 PRED_REGULAR = 1                           # MIP_PRED_REGULAR: flags bit of predict(..., regular=True)
 PRED_ANGULAR = 4                           # MIP_PRED_ANGULAR: flags bit of predict(..., angular=True)
 CHAIN_ANGULAR = 1                          # MIP_CHAIN_ANGULAR: flags bit of mip_predicted_frames_ex (the angular stage)
@@ -154,6 +156,9 @@ def library():
         "mip_extended_refs": (ip, [ip, ip, ip, vp, vp]),
         "mip_angular_refs": (ip, [vp, ip]),
         "mip_angular_refs_get": (ip, [vp]),
+        "mip_angular_interp": (ip, [vp, ip]),
+        "mip_angular_interp_get": (ip, [vp]),
+        "mip_angular_filter": (ip, [ip, ip, ip]),
         "mip_filter_device": (ip, [vp, vp, ip, ip, ip, ip, ip, vp]),
         "mip_copy_device": (ip, [vp, vp, ctypes.c_size_t, vp]),
         "mip_topk_device": (ip, [vp, ip, ip, ip, ip, vp, vp, vp]),
@@ -320,6 +325,21 @@ class MipEngine:
     def angular_refs(self, value):
         with self._lock:
             _check(library().mip_angular_refs(self._h, int(value)))
+
+    @property
+    def angular_interp(self) -> int:
+        """ANG_INTERP_2TAP (the default) or ANG_INTERP_4TAP: the interpolation filter of every angular
+        entry point of this engine (mip_angular_interp), independent of angular_refs.  A call uses
+        the setting it finds when it is made; work already enqueued keeps its own."""
+        with self._lock:
+            value = library().mip_angular_interp_get(self._h)
+            _check(min(value, 0))
+            return value
+
+    @angular_interp.setter
+    def angular_interp(self, value):
+        with self._lock:
+            _check(library().mip_angular_interp(self._h, int(value)))
 
     @property
     def costs_per_frame(self) -> int:
@@ -779,6 +799,14 @@ def unavailable_cus(width, height, filter=None) -> np.ndarray:
     return out.astype(bool)
 
 
+def angular_filter(lw, lh, mode):
+    """0 (cubic) or 1 (Gaussian): the interpolation table a (1 << lw) x (1 << lh) CU takes for the
+    angular mode `mode` with ANG_INTERP_4TAP (mip_angular_filter; host only)."""
+    value = library().mip_angular_filter(int(lw), int(lh), int(mode))
+    _check(min(value, 0))
+    return value
+
+
 def extended_refs(width, height, filter=None):
     """(top, left) uint8 per CU (reference order): how many real samples extend the CU's top line
     (0..h) and its left line (0..w) with ANG_REFS_EXTENDED, for the availability set of an engine
@@ -955,6 +983,6 @@ def filter_device(frames_in, frames_out, filter, kernel_idx=0, stream=None):
     return frames_out
 
 
-__all__ = ["MODE_PLANAR", "MODE_DC", "INTRA_MAX_BIAS", "MODE_ANGULAR_BASE", "ANGULAR_MODES", "ANGULAR_MAX_SEEDS", "ANGULAR_EVEN_MODES", "ANG_REFS_SUBSTITUTED", "ANG_REFS_EXTENDED", "extended_refs", "PRED_REGULAR", "PRED_ANGULAR", "CHAIN_ANGULAR", "PRED_ITEM", "PRED_NONE", "pred_items", "PART_MAX_LEAVES", "PART_MAX_PENALTY", "partition_device", "MipEngine", "MipError", "build_id", "source_id", "FILTERS", "FILTER_NONE", "filter_index", "filter_device", "topk_device", "library",
+__all__ = ["MODE_PLANAR", "MODE_DC", "INTRA_MAX_BIAS", "MODE_ANGULAR_BASE", "ANGULAR_MODES", "ANGULAR_MAX_SEEDS", "ANGULAR_EVEN_MODES", "ANG_REFS_SUBSTITUTED", "ANG_REFS_EXTENDED", "extended_refs", "ANG_INTERP_2TAP", "ANG_INTERP_4TAP", "angular_filter", "PRED_REGULAR", "PRED_ANGULAR", "CHAIN_ANGULAR", "PRED_ITEM", "PRED_NONE", "pred_items", "PART_MAX_LEAVES", "PART_MAX_PENALTY", "partition_device", "MipEngine", "MipError", "build_id", "source_id", "FILTERS", "FILTER_NONE", "filter_index", "filter_device", "topk_device", "library",
            "pinned_empty", "unavailable_cus", "numa_node", "bind_thread", "device_cache", "copy_device",
            "layout", "SHAPES", "COSTS_PER_CTU", "CUS_PER_CTU", "UNAVAILABLE", "num_ctus"]
