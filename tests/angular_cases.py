@@ -17,13 +17,22 @@ FILTER = C.FILTER
 TABLES = ("cost", "sad", "satd")
 EVEN_MODES = tuple(range(2, 67, 2))
 
-# launch_angular (vvc-mip-gpu_amd/csrc/mip_angular.hip) through launch_window_kernel
-# (vvc-mip-gpu_amd/csrc/mip_window_dev.h): grid = min(items, 32 * CUs) over the intra kernel's
-# items -- frames * CTUs * 20, per CTU the four 64x64 CUs, then the sixteen 32x32 blocks.
-# tests/test_angular_cpu.py compares the factor with that function's text.
+# The six angular cost launchers (vvc-mip-gpu_amd/csrc/mip_angular.hip) go through
+# launch_window_kernel (vvc-mip-gpu_amd/csrc/mip_window_dev.h): grid = min(items, 32 * CUs) over the
+# intra kernel's items -- frames * CTUs * 20, per CTU the four 64x64 CUs, then the sixteen 32x32
+# blocks.  tests/test_angular_cpu.py compares the factor with that function's text.
 ANGULAR_ITEMS_PER_CU = 32
 ANGULAR_ITEMS_PER_CTU = launch_caps.INTRA_ITEMS_PER_CTU
 ANGULAR_BIG_ITEMS = launch_caps.INTRA_BIG_ITEMS
+# (launcher, kernel) of that file.  A kernel is a one-line wrapper of COST_BODY, except the two of
+# COST_OWN_BODY, which keep the same walk as a body of their own because they were measured slower
+# as instances of it (tests/test_angular_refine_cpu.py reads the text).
+COST_SOURCE = "mip_angular.hip"
+COST_BODY = "angular_items"
+COST_OWN_BODY = ("angular_ext_kernel", "angular_tap4_kernel")
+COST_KERNELS = (("launch_angular", "angular_kernel"), ("launch_angular_refine", "angular_refine_kernel"),
+                ("launch_angular_ext", "angular_ext_kernel"), ("launch_angular_ext_refine", "angular_ext_refine_kernel"),
+                ("launch_angular_tap4", "angular_tap4_kernel"), ("launch_angular_tap4_refine", "angular_tap4_refine_kernel"))
 
 
 def angular_cap(cus):

@@ -4,9 +4,11 @@ loop and a tail loop that split the work of a pass.  tests/test_gpu_multipass.py
 tests/test_gpu_predict_multipass.py and tests/test_gpu_copy.py size their work from these
 factors so that every workgroup runs at least two passes; the CPU test of
 tests/test_gpu_multipass.py reads the launchers' text and fails when a factor here no longer
-is the launcher's.  The intra kernel and the two angular kernels have one item walk, one window
-staging and one launch rule between them, in WINDOW_HEADER: window_text() is that file, and
-uses_window_rules() says whether a launcher and its kernel go through it.
+is the launcher's.  The intra kernel and the six angular cost kernels have one item walk, one
+window staging and one launch rule between them, in WINDOW_HEADER: window_text() is that file, and
+uses_window_rules() says whether a launcher and the code its kernel runs go through it.  The nine
+angular kernels (six cost kernels, three block outputs) are one-line wrappers of a shared body:
+kernel_body() follows a wrapper to the body it calls, wrapped_body() names that body.
 
   launch_partition (vvc-mip-gpu_amd/csrc/mip_partition.hip): grid = min(groups, 8 * CUs),
       groups = frames * CTUs, one (frame, CTU) pair per pass;
@@ -65,17 +67,35 @@ def window_text():
 
 
 def uses_window_rules(source, launcher, kernel):
-    """`launcher` takes its argument and grid rules, `kernel` its items and staging, from WINDOW_HEADER."""
-    body, code = launcher_body(source, launcher), kernel_body(source, kernel)
+    """`launcher` takes its argument and grid rules, the code of `kernel` its items and staging, from WINDOW_HEADER."""
+    body, code = launcher_function(source, launcher), kernel_body(source, kernel)
     return ("window_args_ok(a)" in body and "return launch_window_kernel(%s, a, s);" % kernel in body and "hipLaunchKernelGGL" not in body
             and "window_item(g, a.nctus, a.ctu_cols, frame_samples, a.orig, a.refs)" in code and "stage_window(it.F, it.R, a.width," in code)
 
 
+def launcher_function(source, launcher):
+    """The text of `launcher` alone, from its signature to the closing brace of its body."""
+    text = launcher_body(source, launcher)
+    return text[:text.index("\n}\n")]
+
+
+WRAPPER = r"__global__ [^;{}]*\bvoid %s\(\w+ a\) \{ (\w+)<[\w, ]+>\(a\); \}\n"
+
+
+def wrapped_body(source, kernel):
+    """The shared body that `kernel` is a one-line wrapper of (nothing but its call, the kernel's
+    argument struct handed on as it is), or None where the kernel has a body of its own."""
+    with open(os.path.join(CSRC, source)) as f:
+        m = re.search(WRAPPER % kernel, f.read())
+    return m.group(1) if m else None
+
+
 def kernel_body(source, kernel):
-    """The text of `kernel` in csrc/`source`, from its name to the closing brace of its body."""
+    """The text of the code `kernel` runs in csrc/`source`: its own body from its name to the closing
+    brace, or that of the shared body it wraps."""
     with open(os.path.join(CSRC, source)) as f:
         text = f.read()
-    at = text.index("void %s(" % kernel)
+    at = text.index("void %s(" % (wrapped_body(source, kernel) or kernel))
     return text[at:text.index("\n}\n", at)]
 
 

@@ -319,23 +319,23 @@ def _kernel(name):
 
 
 def test_kernel_resources():
-    """The three new kernels: no scratch, no spilled vector register; the two cost kernels three
-    waves per SIMD like their siblings (at most 168 VGPRs, 3 x LDS <= 160 KB).  The figures are the
-    build's, pinned: the lane index formed per item keeps per-lane addresses out of registers held
-    across an item, which is why they are below the siblings'.
-    angular_kernel is what it was."""
+    """The three _ext kernels: no scratch, no spilled vector register; the two cost kernels three
+    waves per SIMD like their siblings (at most 168 VGPRs, 3 x LDS <= 160 KB); LDS exactly what the
+    layouts add up to -- 400 bytes of line extensions in the cost kernels, 5G + 4 words per group in
+    the block output.  The VGPR figures themselves are pinned in
+    tests/test_kernel_resources.py."""
     mipgpu.library()
-    want = {"angular_ext_kernel": (133, 13708), "angular_ext_refine_kernel": (156, 14012), "angular_ext_predict_kernel": (78, 5376)}
-    for name, (vgprs, lds) in want.items():
+    want = {"angular_ext_kernel": 13708, "angular_ext_refine_kernel": 14012, "angular_ext_predict_kernel": 5376}
+    for name, lds in want.items():
         k = _kernel(name)
         assert k[".private_segment_fixed_size"] == 0 and k.get(".vgpr_spill_count", 0) == 0, name
-        assert (k[".vgpr_count"] + k.get(".agpr_count", 0), k[".group_segment_fixed_size"]) == (vgprs, lds), name
+        assert k[".group_segment_fixed_size"] == lds, name
     for name in ("angular_ext_kernel", "angular_ext_refine_kernel"):
         k = _kernel(name)
         assert k[".vgpr_count"] + k.get(".agpr_count", 0) <= 168 and 3 * k[".group_segment_fixed_size"] <= 160 * 1024
     plain = _kernel("angular_kernel")
-    assert (plain[".vgpr_count"], plain[".group_segment_fixed_size"], plain[".private_segment_fixed_size"]) == (150, 13308, 0)
-    # the new kernels' names stay clear of the patterns other tests find the existing kernels by
+    assert (plain[".group_segment_fixed_size"], plain[".private_segment_fixed_size"]) == (13308, 0)
+    # the _ext kernels' names stay clear of the patterns other tests find their siblings by
     for name in kernel_resources.kernels(mipgpu.LIB_PATH):
         if "_ext_" in name:
             assert not re.search(r"\d+(angular_kernel|angular_refine_kernel|intra_kernel)E", name), name

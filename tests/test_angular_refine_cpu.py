@@ -275,20 +275,29 @@ def test_entry_points_refuse_a_null_engine():
 
 def test_launch_cap_is_the_angular_launcher_s():
     """launch_angular_refine: angular_kernel's items and grid cap (tests/angular_cases.angular_cap
-    sizes the multi-pass GPU test), and angular_kernel's item walk: both launchers and both kernels
-    go through the one grid rule and item walk of launch_caps.WINDOW_HEADER, and neither file has
-    a cap or an item count of its own."""
-    assert launch_caps.uses_window_rules("mip_angular.hip", "launch_angular", "angular_kernel")
-    assert launch_caps.uses_window_rules("mip_angular_refine.hip", "launch_angular_refine", "angular_refine_kernel")
+    sizes the multi-pass GPU test), and angular_kernel's item walk: all six launchers and the code
+    all six cost kernels run -- the one body four of them wrap, the own bodies of the other two -- go
+    through the one grid rule and item walk of launch_caps.WINDOW_HEADER, and no angular file has a
+    cap or an item count of its own."""
+    for launcher, kernel in AC.COST_KERNELS:
+        assert launch_caps.uses_window_rules(AC.COST_SOURCE, launcher, kernel), launcher
+        # nothing but a call of the shared body -- or, for the two measured slower that way, no wrapper at all
+        assert launch_caps.wrapped_body(AC.COST_SOURCE, kernel) == (None if kernel in AC.COST_OWN_BODY else AC.COST_BODY), kernel
     body = launch_caps.launcher_body(launch_caps.WINDOW_HEADER, "launch_window_kernel")
     caps = launch_caps.CAP_EXPRESSION.findall(body)
     assert caps == [(str(AC.ANGULAR_ITEMS_PER_CU),) * 2], caps
     assert "a.nframes * a.nctus * kItemsPerCtu" in body
-    for source in ("mip_angular.hip", "mip_angular_refine.hip"):
+    sources = sorted(f for f in os.listdir(launch_caps.CSRC) if f.startswith("mip_angular"))
+    assert sources == ["mip_angular.hip", "mip_angular_dev.h"]
+    walks = 0
+    for source in sources:
         with open(launch_caps.CSRC + "/" + source) as f:
             own = f.read()
         assert not launch_caps.CAP_EXPRESSION.findall(own) and "kItemsPerCtu =" not in own and "big = k <" not in own, source
-    kernel = launch_caps.kernel_body("mip_angular_refine.hip", "angular_refine_kernel")
+        walks += own.count("g += gridDim.x")
+    assert walks == 1 + len(AC.COST_OWN_BODY)                               # the item loop: the shared body's, and the two own bodies'
+    kernel = launch_caps.kernel_body(AC.COST_SOURCE, "angular_refine_kernel")
+    assert kernel.startswith("void %s(" % AC.COST_BODY)
     text = launch_caps.window_text()
     assert "g += gridDim.x" in kernel and text.count("const bool big = k < %d;" % AC.ANGULAR_BIG_ITEMS) == 1
     assert text.count("constexpr int kItemsPerCtu = 4 + kIntraBlocks;") == 1
@@ -303,14 +312,14 @@ def _kernel(name):
 def test_kernel_resources():
     """angular_refine_kernel: no scratch, no spilled vector register, at most 168 VGPRs -- 512 per
     SIMD lane over three waves, in the allocation unit of 8 -- so three waves per SIMD like
-    angular_kernel, whose own figures stay what they were."""
+    angular_kernel; both with exactly the LDS of their layouts.  The VGPR figures themselves are
+    pinned in tests/test_kernel_resources.py."""
     mipgpu.library()
-    k = _kernel("angular_refine_kernel")
-    assert k[".private_segment_fixed_size"] == 0 and k.get(".vgpr_spill_count", 0) == 0
-    assert k[".vgpr_count"] + k.get(".agpr_count", 0) <= 512 // 3 // 8 * 8 == 168
-    assert 3 * k[".group_segment_fixed_size"] <= 160 * 1024
-    plain = _kernel("angular_kernel")
-    assert (plain[".vgpr_count"], plain[".group_segment_fixed_size"], plain[".private_segment_fixed_size"]) == (150, 13308, 0)
+    for name, lds in (("angular_refine_kernel", 13612), ("angular_kernel", 13308)):
+        k = _kernel(name)
+        assert k[".private_segment_fixed_size"] == 0 and k.get(".vgpr_spill_count", 0) == 0, name
+        assert k[".vgpr_count"] + k.get(".agpr_count", 0) <= 512 // 3 // 8 * 8 == 168, name
+        assert k[".group_segment_fixed_size"] == lds and 3 * lds <= 160 * 1024, name
 
 
 def test_gpu_case_set_is_not_vacuous():

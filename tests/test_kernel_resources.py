@@ -15,8 +15,15 @@ objects' metadata, tests/kernel_resources.py).
   CU, 4 waves per SIMD: <= 128 VGPRs.
 * intra_kernel, the first of the kernels that cost every CU from a staged window and share
   their item walk and staging (csrc/mip_window_dev.h): <= 128 VGPRs, 4 waves per SIMD, no
-  scratch.  Its angular siblings, at 3 waves per SIMD, are pinned in
-  tests/test_angular_refine_cpu.py.
+  scratch.
+* The angular family -- six cost kernels, four of them one body with a policy and two with the
+  same walk as a body of their own (csrc/mip_angular.hip), three block outputs that are one body
+  with a policy (csrc/mip_predict_angular.hip): no scratch, no spilled vector
+  register; the cost kernels three waves per SIMD (at most 168 VGPRs, 3 x LDS <= 160 KB); LDS
+  exactly what the layouts add up to; and the build's VGPR figures, pinned with equality in
+  ANGULAR_FAMILY below, the one table of them (DESIGN.md section 5.7 has it beside the figures of
+  the six separate bodies it replaced).  tests/test_angular_refine_cpu.py, test_angular_ext_cpu.py
+  and test_angular_tap4_cpu.py hold their kernels to the same conditions by name.
 """
 import os
 import re
@@ -83,3 +90,29 @@ def test_intra_kernel_occupancy(kernels):
     (name, k), = found.items()
     assert k[".vgpr_count"] + k.get(".agpr_count", 0) <= 128, (name, k[".vgpr_count"])
     assert k[".private_segment_fixed_size"] == 0 and k.get(".vgpr_spill_count", 0) == 0, name
+
+
+# kernel: (VGPRs, AGPRs included; LDS bytes).  LDS is the layout's: s_org 8192, s_ref 2256 (2656 with the
+# two line extensions), s_sum 2080, s_tab 780; the refinement's s_pack 260 and s_cand 28 (and
+# padding), the four taps' s_coef 256 -- an instantiation without one of them does not pay for it.
+# Block output: 4 waves x 272 (336 with the extension) words, the four taps' 256 bytes.
+# (angular_ext_kernel and angular_tap4_kernel keep a body of their own, and with it their earlier figures.)
+ANGULAR_COST = {"angular_kernel": (124, 13308), "angular_refine_kernel": (131, 13612),
+                "angular_ext_kernel": (133, 13708), "angular_ext_refine_kernel": (138, 14012),
+                "angular_tap4_kernel": (147, 13968), "angular_tap4_refine_kernel": (147, 14268)}
+ANGULAR_OUTPUT = {"angular_predict_kernel": (63, 4352), "angular_ext_predict_kernel": (78, 5376), "angular_tap4_predict_kernel": (78, 5632)}
+ANGULAR_FAMILY = {**ANGULAR_COST, **ANGULAR_OUTPUT}
+
+
+def test_angular_family_resources(kernels):
+    got = {}
+    for name in ANGULAR_FAMILY:
+        found = [k for n, k in kernels.items() if re.search(r"\d+%sE" % name, n)]
+        assert len(found) == 1, name
+        k, = found
+        assert k[".private_segment_fixed_size"] == 0 and k.get(".vgpr_spill_count", 0) == 0, name
+        got[name] = (k[".vgpr_count"] + k.get(".agpr_count", 0), k[".group_segment_fixed_size"])
+    assert got == ANGULAR_FAMILY
+    for name in ANGULAR_COST:
+        assert got[name][0] <= 512 // 3 // 8 * 8 == 168 and 3 * got[name][1] <= 160 * 1024, name
+    assert len([n for n in kernels if "angular" in n]) == len(ANGULAR_FAMILY)      # nine kernels, no stray instance

@@ -1,12 +1,13 @@
-"""Angular block output on the CPU (no GPU): the write rule the two prediction kernels share
+"""Angular block output on the CPU (no GPU): the write rule the prediction kernels share
 (csrc/predict_rule.h), compiled stand-alone (tests/cpp/test_predict_rule.cpp, with
 -fsanitize=address,undefined; no preloaded library) on arrays of exactly the sizes the rule may
 index, equals a numpy restatement written from the contract text of include/mipgpu.h for every
 flag combination; the same program checks the argument rules of the flags word and of
 mip_predicted_frames_ex.  The constants the multi-pass GPU test is sized from
-(tests/predict_angular_caps.py) are the launcher's and the kernel's, read from their text; the
-existing launcher and kernel of mip_predict.hip keep exactly two instances of one kernel; and the
-Python constants mirror the header."""
+(tests/predict_angular_caps.py) are the shared launch's and the shared body's, read from their
+text, and the three angular kernels and launchers are nothing but calls of those; the existing
+launcher and kernel of mip_predict.hip keep exactly two instances of one kernel; and the Python
+constants mirror the header."""
 import inspect
 import os
 import re
@@ -30,16 +31,25 @@ def test_angular_predict_caps_are_the_launchers():
     assert "constexpr int kAngPredWaves = %d;" % L.WAVES in text
     assert "constexpr int kAngPredEntriesPerWave = %d;" % L.ENTRIES_PER_WAVE in text
     assert "constexpr int kAngPredGroupsCap = %d;" % L.GROUPS_CAP in text
-    body = L.launcher_body(L.SOURCE, L.LAUNCHER)
+    body = L.launcher_body(L.SOURCE, L.LAUNCH_RULE)                       # (to the end of the file: the three launchers too)
     assert "per_group = (long long)kAngPredWaves * kAngPredEntriesPerWave;" in body
     assert "groups = std::min<long long>((a.n + per_group - 1) / per_group, kAngPredGroupsCap);" in body
-    assert body.count("dim3((unsigned)groups), dim3(64 * kAngPredWaves)") == 1 and body.count("hipLaunchKernelGGL(") == 1
+    assert body.count("dim3((unsigned)groups), dim3(64 * kAngPredWaves)") == 1 and text.count("hipLaunchKernelGGL(") == 1
     assert "cus" not in body and "multiProcessorCount" not in text       # the cap does not depend on the device
+    for launcher, kernel, ext_ok in L.LAUNCHERS:                          # every launcher is a call of that launch with its kernel
+        assert "return %s(%s, a, %s, s);" % (L.LAUNCH_RULE, kernel, ext_ok) in L.launcher_function(L.SOURCE, launcher), launcher
+        assert L.wrapped_body(L.SOURCE, kernel) == L.BODY, kernel         # and every kernel nothing but a call of the one body
     kernel = L.kernel_body(L.SOURCE, L.KERNEL)
+    assert kernel.startswith("void %s(" % L.BODY)
     assert "rows = (a.n + kAngPredEntriesPerWave - 1) / kAngPredEntriesPerWave;" in kernel
     assert "r = (long long)blockIdx.x * kAngPredWaves + wv; r < rows; r += (long long)gridDim.x * kAngPredWaves" in kernel
     assert "idx = r * kAngPredEntriesPerWave + lane;" in kernel and "lane = threadIdx.x & 63" in kernel
-    assert "__syncthreads" not in text                                    # wave-private LDS: no workgroup barrier
+    assert text.count("atomicSub(a.skipped") == 1 == kernel.count("atomicSub(a.skipped")      # one list scan in the block-output sources
+    for once in ("Item take_item(", "void store_angular(", "void predict_angular_cu(", "void wave_lds_sync("):
+        assert text.count(once) == 1, once
+    # wave-private LDS: no workgroup barrier in the scan -- the only one stands before it, behind the 4-tap coefficients' staging
+    assert text.count("__syncthreads()") == 1 == kernel.count("__syncthreads()")
+    assert kernel.index("s_coef[threadIdx.x] = a.coef[threadIdx.x];") < kernel.index("__syncthreads()") < kernel.index("for (long long r =")
     assert L.ENTRIES_PER_WAVE == 64                                       # one entry per lane of a wave
     assert L.ENTRIES_PER_ROUND == L.GROUPS_CAP * L.WAVES * L.ENTRIES_PER_WAVE == 262144
     assert L.ROWS_PER_ROUND * L.ENTRIES_PER_WAVE == L.ENTRIES_PER_ROUND
@@ -49,16 +59,16 @@ def test_angular_predict_caps_are_the_launchers():
 
 
 def test_the_mip_kernel_and_its_launcher_are_left_alone():
-    """The angular kernel is a file and a launcher of its own: launch_predict still launches two
+    """The angular kernels are a file and launchers of their own: launch_predict still launches two
     instances of predict_kernel and nothing else, and the shared rule is the one function both
-    kernels call."""
+    files' kernels call."""
     body = L.launcher_body("mip_predict.hip", "launch_predict")
     assert body.count("hipLaunchKernelGGL(") == 2 and "angular" not in body
     with open(os.path.join(L.CSRC, "mip_predict.hip")) as f:
         mip = f.read()
     with open(os.path.join(L.CSRC, L.SOURCE)) as f:
         ang = f.read()
-    assert "pred_decode<REGULAR, false>(a, it, PredShapes{})" in mip and "pred_decode<false, true>(a, a.items[idx], AngShapes{})" in ang
+    assert "pred_decode<REGULAR, false>(a, it, PredShapes{})" in mip and "pred_decode<false, true>(a, it, AngShapes{})" in ang
     for text in (mip, ang):
         assert '#include "predict_rule.h"' in text and "it.pitch <" not in text    # no copy of the rule
     with open(os.path.join(L.CSRC, "host_stages.cpp")) as f:

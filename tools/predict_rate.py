@@ -8,8 +8,9 @@ every mode of every 16x16 CU of one frame.  Those four go through mip_predict_de
 kernel instance).  Two more go through mip_predict_device_ex with MIP_PRED_REGULAR: Planar for every
 available 16x16 CU, and the item list mip_partition_device writes for the 16 frames after the
 Planar / DC merge (bias CHAIN_BIAS, penalty CHAIN_PENALTY; padding entries included, as a caller
-that makes no host round trip passes it).  With MIP_PRED_ANGULAR (the second kernel,
-mip_predict_angular.hip, behind the first): every available 16x16 CU with one angular mode of each
+that makes no host round trip passes it).  With MIP_PRED_ANGULAR (the second kernel behind the
+first: mip_predict_angular.hip's one block-output body, the instance the engine's mip_angular_refs
+and mip_angular_interp settings select): every available 16x16 CU with one angular mode of each
 class and sign in turn (modes 6, 27, 41, 60), frame layout; the list the partition writes after the
 Planar / DC merge and the merge of all 65 angular modes (bias 0), predicted with both flags; and a
 list of the same entry count that is padding only, with MIP_PRED_REGULAR alone and with both flags

@@ -1,10 +1,10 @@
 // angular_plan.h -- the directional (angular) intra costs (include/mipgpu.h, mip_angular_device)
-// as per-sample and per-4x4-block arithmetic, shared by the kernel (mip_angular.hip: one lane per
+// as per-sample and per-4x4-block arithmetic, shared by the kernels (mip_angular.hip: one lane per
 // 4x4 block, a wave-uniform loop over the mode list) and by the host restatement below
 // (angular_frames_host: the same steps, one CU at a time), plus the argmin over the list and the
 // decision merge.  Reference samples, SAD, SATD and cost are intra_plan.h's.  No HIP dependency
 // on the host side; unit-tested by tests/cpp/test_angular_plan.cpp.
-// The coarse-to-fine search (mip_angular_refine_device, mip_angular_refine.hip) adds the running
+// The coarse-to-fine search (mip_angular_refine_device, the same file's refinement pass) adds the running
 // top three of the list, the seed and candidate step, and its own host walk
 // (angular_refine_frames_host); unit-tested by tests/cpp/test_angular_refine.cpp.
 //

@@ -1,7 +1,9 @@
 // mip_kernels.h -- launch interface between the C-ABI host code (mipgpu.cpp, host_pipeline.cpp)
 // and the gfx950 kernels (mip_search.hip, mip_decide.hip, mip_filter.hip, mip_fixup.hip,
 // mip_predict.hip, mip_predict_angular.hip, mip_partition.hip, mip_intra.hip, mip_angular.hip,
-// mip_angular_refine.hip, mip_angular_ext.hip, mip_predict_angular_ext.hip, mip_candidates.hip).
+// mip_candidates.hip).  The angular family is nine kernels from two bodies: six cost kernels in
+// mip_angular.hip and three block outputs in mip_predict_angular.hip, each a body with a policy for
+// the reference lines and the interpolation; the argument structs below grow by derivation.
 // Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -183,7 +185,8 @@ struct PredictArgs {
                               // (launches the kernel's second instance; 0: the MIP-only one)
 };
 hipError_t launch_predict(const PredictArgs &a, hipStream_t s);
-// MIP_PRED_ANGULAR (angular_predict_kernel, mip_predict_angular.hip): the items of the same list
+// MIP_PRED_ANGULAR (angular_predict_kernel, mip_predict_angular.hip: the block-output body with
+// substituted lines and two taps): the items of the same list
 // whose mode is an angular code.  Launched behind launch_predict on the same stream: it emits what
 // that kernel rejected and counted, and takes one off a.skipped for every item it emits
 // (refs_vec and regular are not used).
@@ -221,8 +224,8 @@ struct IntraArgs {
 hipError_t launch_intra(const IntraArgs &a, hipStream_t s);
 
 // Angular intra costs, the best angular mode and its merge into the decisions (angular_kernel,
-// mip_angular.hip): the work items, window and lane slots of the intra kernel, a wave-uniform
-// loop over the mode list.
+// mip_angular.hip: the cost body with substituted lines and two taps, no refinement): the work
+// items, window and lane slots of the intra kernel, a wave-uniform loop over the mode list.
 struct AngularArgs {
   const uint16_t *orig;       // as IntraArgs
   const uint16_t *refs;
@@ -242,8 +245,9 @@ struct AngularArgs {
 };
 hipError_t launch_angular(const AngularArgs &a, hipStream_t s);
 
-// Coarse-to-fine angular search (angular_refine_kernel, mip_angular_refine.hip): angular_kernel's
-// items, window and coarse loop, then per CU the +-1 neighbours of its own best `nseeds` modes.
+// Coarse-to-fine angular search (angular_refine_kernel: the same body with its refinement pass):
+// angular_kernel's items, window and coarse loop, then per CU the +-1 neighbours of its own best
+// `nseeds` modes.
 struct AngularRefineArgs : AngularArgs {
   uint8_t *tried;             // optional: [nframes][nctus * 5380] modes evaluated per CU
   int nseeds;                 // min(seeds, nmodes): 1..3
@@ -252,10 +256,11 @@ struct AngularRefineArgs : AngularArgs {
 hipError_t launch_angular_refine(const AngularRefineArgs &a, hipStream_t s);
 
 // The angular family with extended reference lines (mip_angular_refs MIP_ANG_REFS_EXTENDED):
-// angular_ext_kernel and angular_ext_refine_kernel (mip_angular_ext.hip) are angular_kernel and
-// angular_refine_kernel with the two line extensions staged and each CU's main line lengthened by
-// its entry of `ext`; angular_ext_predict_kernel (mip_predict_angular_ext.hip) is
-// angular_predict_kernel with the longer per-item line.  The launch rules are their siblings'.
+// angular_ext_kernel and angular_ext_refine_kernel are the cost body with the policy that stages
+// the two line extensions and lengthens each CU's main line by its entry of `ext`;
+// angular_ext_predict_kernel is the block-output body with the longer per-item line.  The launch
+// rules are the family's; `ext` is required.  (angular_ext_kernel and angular_tap4_kernel have that
+// walk and policy written out as a body of their own: mip_angular.hip says why.)
 struct AngularExtArgs : AngularRefineArgs {  // (the plain launch does not look at tried, nseeds, all)
   const uint16_t *ext;        // [nctus * 5380] E_top | E_left << 8 (mip_extended_refs, the set of unavail)
 };
@@ -267,11 +272,10 @@ struct PredictExtArgs : PredictArgs {
 hipError_t launch_predict_angular_ext(const PredictExtArgs &a, hipStream_t s);
 
 // The angular family with VVC's 4-tap luma interpolation (mip_angular_interp MIP_ANG_INTERP_4TAP):
-// angular_tap4_kernel and angular_tap4_refine_kernel (mip_angular_tap4.hip) are the two _ext cost
-// kernels and angular_tap4_predict_kernel (mip_predict_angular_tap4.hip) the _ext block output,
-// with the line P = ... of the predictor replaced.  One kernel per role serves both
-// mip_angular_refs settings: ext == NULL is MIP_ANG_REFS_SUBSTITUTED (every length 0).  The launch
-// rules are their siblings'.
+// angular_tap4_kernel and angular_tap4_refine_kernel are the cost body and
+// angular_tap4_predict_kernel the block-output body with the _ext policies' lines and the line
+// P = ... of the predictor replaced.  One kernel per role serves both mip_angular_refs settings:
+// ext == NULL is MIP_ANG_REFS_SUBSTITUTED (every length 0).  The launch rules are the family's.
 struct AngularTap4Args : AngularExtArgs {  // (ext may be NULL)
   uint32_t coef[64];          // angular_plan.h ang_coef_word at G << 5 | f (staged in LDS: a per-lane lookup)
 };

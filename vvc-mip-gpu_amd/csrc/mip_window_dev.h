@@ -1,5 +1,5 @@
 // mip_window_dev.h -- what the kernels that cost every CU of a frame from a staged window share
-// (intra_kernel in mip_intra.hip; angular_kernel and angular_refine_kernel through
+// (intra_kernel in mip_intra.hip; the six angular cost kernels of mip_angular.hip, one body, through
 // mip_angular_dev.h): the work items, the window staging, the window as a Ref, the group sum, a
 // lane's originals, and the launchers' common argument and grid rules.  Internal linkage: each
 // kernel file has its own copies.  DESIGN.md section 5.6.
@@ -15,10 +15,11 @@
 // and then walks the block's lane slots (intra_plan.h intra_build_slots): one lane per 4x4 block
 // of a CU, a CU's lanes an aligned power-of-two group of one wave.
 //
-// The device helpers take pointers and scalars, not a reference to a kernel's argument struct (a
-// staging helper that took one left the angular kernels with 20 bytes of private segment per
-// lane), and their form is the one in which the three kernels keep their registers and the code
-// of their loops: DESIGN.md section 5.6, "One copy".
+// The device helpers here take pointers and scalars, not a reference to a kernel's argument struct
+// (a staging helper that took one left the angular kernels with 20 bytes of private segment per
+// lane), and their form is the one in which the kernels keep their registers and the code of
+// their loops: DESIGN.md section 5.6, "One copy".  (The angular kernels' shared body, inlined into
+// each one-line kernel, does take the struct by const reference: mip_angular_dev.h.)
 #pragma once
 #include "intra_plan.h"
 #include "mip_kernels.h"
@@ -118,7 +119,7 @@ __device__ __forceinline__ void load_org(const uint16_t *s_org, int lp, const In
   load_org(s_org + ((4 * c.cy + 4 * c.bj) << lp) + 4 * c.cx + 4 * c.bi, lp, org);
 }
 
-// ---- host side: what the three launchers share.  The argument rules every one of them has; each
+// ---- host side: what the launchers share.  The argument rules every one of them has; each
 // adds its own (its mode list, its seeds, "at least one output").
 template <class Args>
 inline bool window_args_ok(const Args &a) {

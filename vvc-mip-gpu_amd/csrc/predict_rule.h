@@ -1,6 +1,6 @@
 // predict_rule.h -- the write rule of the prediction output (include/mipgpu.h, mip_predict_device_ex)
-// as one function, shared by the two kernels that walk a device list (mip_predict.hip: MIP, Planar
-// and DC items; mip_predict_angular.hip: angular items) and, with the argument rules of the flags
+// as one function, shared by the kernels that walk a device list (mip_predict.hip: MIP, Planar
+// and DC items; mip_predict_angular.hip: angular items, three kernels of one body) and, with the argument rules of the flags
 // word and of mip_predicted_frames_ex, by the host code.  No HIP dependency on the host side;
 // unit-tested by tests/cpp/test_predict_rule.cpp.
 #pragma once
