@@ -13,6 +13,7 @@ import intra_cases as C
 import mipgpu
 import oracle_lib as O
 import size_sweep as S
+from mipgpu import layout
 
 SIZE = (264, 136)                                             # 3 x 2 CTUs, partial right column and bottom row
 FILTER_2D = "filterFrame_2d_int_quarterCtu"                   # the engine filter of the GPU cases
@@ -45,6 +46,27 @@ def lengths(w, h, filt=None):
     un = mipgpu.unavailable_cus(w, h, filt)
     e_top, e_left = X.lengths(w, h, un, undefined(w, h, filt))
     return _freeze(un, e_top, e_left)
+
+
+def length_class(e, full):
+    """0: no extension, 1: a partial one, 2: the full one."""
+    return np.where(e == 0, 0, np.where(e == full, 2, 1))
+
+
+def length_class_cus(w, h, un, e_top, e_left, per=2):
+    """The selector of the block-output tests: `per` CUs of every shape for each of the nine
+    combinations of full / partial / zero lengths on the two lines that exists among the available
+    CUs.  Sorted CU indexes."""
+    shape, x, y, bw, bh = layout.cu_geometry(w, h, np.arange(un.size))
+    kt, kl = length_class(e_top, bh), length_class(e_left, bw)
+    picked = []
+    for s in layout.SHAPES:
+        for a in range(3):
+            for b in range(3):
+                k = np.nonzero(~un & (shape == s.index) & (kt == a) & (kl == b))[0]
+                if k.size:
+                    picked += list(k[np.unique(np.linspace(0, k.size - 1, per).astype(int))])
+    return np.array(sorted(set(picked)), np.int64)
 
 
 def _tables(f, refs, un, e_top, e_left, modes):

@@ -154,20 +154,10 @@ def test_refine_kernel(gpu_available):
 # ---------------------------------------------------------------- 3. block output
 def _block_cus(un, e_top, e_left, per=2):
     """CUs of every shape over the nine combinations of full / partial / zero lengths, where they exist."""
-    shape, x, y, bw, bh = layout.cu_geometry(W, H, np.arange(un.size))
-    kind = lambda e, full: np.where(e == 0, 0, np.where(e == full, 2, 1))
-    kt, kl = kind(e_top, bh), kind(e_left, bw)
-    picked, seen = [], set()
-    for s in layout.SHAPES:
-        for a in range(3):
-            for b in range(3):
-                k = np.nonzero(~un & (shape == s.index) & (kt == a) & (kl == b))[0]
-                if k.size:
-                    seen.add((a, b))
-                    picked += list(k[np.unique(np.linspace(0, k.size - 1, per).astype(int))])
-    assert {a for a, _ in seen} == {0, 1, 2} == {b for _, b in seen}
-    picked = np.array(sorted(set(picked)))
-    assert set(shape[picked]) == set(range(layout.NUM_SHAPES))
+    picked = XC.length_class_cus(W, H, un, e_top, e_left, per)
+    shape, _, _, bw, bh = layout.cu_geometry(W, H, picked)
+    assert set(XC.length_class(e_top[picked], bh)) == {0, 1, 2} == set(XC.length_class(e_left[picked], bw))
+    assert set(shape) == set(range(layout.NUM_SHAPES))
     return picked
 
 

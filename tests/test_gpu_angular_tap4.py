@@ -168,18 +168,8 @@ def test_refine_kernel(gpu_available, refs_setting):
 # ---------------------------------------------------------------- 3. block output
 def _block_cus(un, e_top, e_left, per=2):
     """CUs of every shape over the combinations of full / partial / zero lengths that exist."""
-    shape, x, y, bw, bh = layout.cu_geometry(W, H, np.arange(un.size))
-    kind = lambda e, full: np.where(e == 0, 0, np.where(e == full, 2, 1))
-    kt, kl = kind(e_top, bh), kind(e_left, bw)
-    picked = []
-    for s in layout.SHAPES:
-        for a in range(3):
-            for b in range(3):
-                k = np.nonzero(~un & (shape == s.index) & (kt == a) & (kl == b))[0]
-                if k.size:
-                    picked += list(k[np.unique(np.linspace(0, k.size - 1, per).astype(int))])
-    picked = np.array(sorted(set(picked)))
-    assert set(shape[picked]) == set(range(layout.NUM_SHAPES))
+    picked = TC.XC.length_class_cus(W, H, un, e_top, e_left, per)
+    assert set(layout.cu_geometry(W, H, picked)[0]) == set(range(layout.NUM_SHAPES))
     return picked
 
 

@@ -6,7 +6,6 @@ exactly what each accepted item alone writes under every flag combination with a
 count, the 8-byte store path and unaligned rows give the same samples, the whole device chain
 predicts every leaf, and the angular kernel's grid-stride loop is run beyond two rounds."""
 import ctypes
-from functools import lru_cache
 
 import numpy as np
 import pytest
@@ -17,18 +16,15 @@ import intra_cases as C
 import intra_ref as I
 import mipgpu
 import predict_angular_caps as L
+import predict_angular_variant_cases as V
 import predict_ref as P
 from mipgpu import MipEngine, layout
+from predict_angular_variant_cases import (ALL_CODES, ANG_KINDS, BAD_KINDS, BASE, FILL, PER_BAD_KIND, REGULAR,  # the lists, selectors and
+                                           angular_blocks, regular_blocks)                                     # expected blocks live there
 
 pytestmark = pytest.mark.gpu
 
 FILTER_2D = "filterFrame_2d_float_5x5_quarterCtu"
-FILL = 0xABCD
-PREFIX = np.cumsum([0] + [s.ncu for s in layout.SHAPES])
-BASE = mipgpu.MODE_ANGULAR_BASE
-ALL_CODES = BASE + np.arange(2, 67)
-REGULAR = (I.MODE_PLANAR, I.MODE_DC)
-PADDING = (-1, -1, -1, 0, 0)                                  # what mip_partition_device pads its list with
 
 
 def _dev(a):
@@ -57,37 +53,6 @@ def _is_angular(mode):
     return (mode >= BASE + 2) & (mode <= BASE + 66)
 
 
-def angular_blocks(refs, w, h, cus, modes=None):
-    """{cu: uint16 [len(modes), bh, bw]} -- the blocks of angular_ref.predict on
-    angular_ref.boundaries of refs [H, W] for the modes `modes` (None: all 65, slot m - 2)."""
-    cus = np.asarray(cus, np.int64)
-    shape, x, y, _, _ = layout.cu_geometry(w, h, cus)
-    out = {}
-    for s in layout.SHAPES:
-        sel = np.nonzero(shape == s.index)[0]
-        if sel.size:
-            top, left, corner = A.boundaries(refs, x[sel], y[sel], s.w, s.h)
-            blocks = A.predict(top, left, corner, s.w, s.h, modes).astype(np.uint16)
-            for j, i in enumerate(sel):
-                out[int(cus[i])] = blocks[:, j]
-    return out
-
-
-def regular_blocks(refs, w, h, cus):
-    """{cu: uint16 [2, bh, bw]} -- Planar and DC from intra_ref.predict on predict_ref.boundaries."""
-    cus = np.asarray(cus, np.int64)
-    shape, x, y, _, _ = layout.cu_geometry(w, h, cus)
-    out = {}
-    for s in layout.SHAPES:
-        sel = np.nonzero(shape == s.index)[0]
-        if sel.size:
-            b = [P.boundaries(refs, x[i], y[i], s.w, s.h)[:2] for i in sel]
-            planar, dc = I.predict(np.stack([t for t, _ in b]), np.stack([l for _, l in b]), s.w, s.h)
-            for j, i in enumerate(sel):
-                out[int(cus[i])] = np.stack([planar[j], dc[j]]).astype(np.uint16)
-    return out
-
-
 def _predict_ex(eng, d_frames, d_items, n, out, out_samples, sk, flags, refs=None):
     """mip_predict_device_ex with an explicit flags word; returns the status."""
     import torch
@@ -99,13 +64,7 @@ def _predict_ex(eng, d_frames, d_items, n, out, out_samples, sk, flags, refs=Non
 
 
 # ---------------------------------------------------------------- 1. every shape, every mode
-@lru_cache(maxsize=None)
-def _shape_case():
-    w, h = 264, 136
-    frame = C.frames(w, h, 2)[1]
-    un = mipgpu.unavailable_cus(w, h)
-    cus = P.sample_cus(w, h, un)
-    return w, h, frame, un, cus, angular_blocks(frame, w, h, cus)
+_shape_case = V.shape_case
 
 
 def test_every_shape_every_mode(gpu_available):
@@ -156,16 +115,7 @@ def test_blocks_reproduce_the_engines_angular_tables(gpu_available, filt, which)
     frame = C.frames(w, h, 3)[which]
     if filt == C.FILTER:
         assert E.max_boundary_or_corner(O.filter_frame(frame, filt, 0), mipgpu.unavailable_cus(w, h, filt), w, h) > 1023
-    nct = layout.num_ctus(w, h)
-    un = mipgpu.unavailable_cus(w, h, filt).reshape(nct, layout.CUS_PER_CTU)
-    names = ["ALL_AL_64x64", "ALL_AL_4x32", "ALL_AL_32x4", "ALL_AL_16x16", "ALL_NA_8x32_G2", "ALL_AL_4x4"]
-    lists = []
-    for n in names:
-        s = layout.SHAPE_BY_NAME[n]
-        ctu, c = np.nonzero(~un[:, PREFIX[s.index]:PREFIX[s.index + 1]])
-        assert c.size
-        k = ctu * layout.CUS_PER_CTU + PREFIX[s.index] + c
-        lists.append((s, k[np.unique(np.linspace(0, k.size - 1, 8 if s.w == 64 else 40).astype(int))]))
+    lists = V.table_lists(w, h, filt)
     cu = np.concatenate([np.repeat(k, 65) for _, k in lists])
     mode = np.concatenate([np.tile(ALL_CODES, k.size) for _, k in lists])
     items, total = mipgpu.pred_items(w, h, 0, cu, mode)
@@ -192,62 +142,7 @@ def test_blocks_reproduce_the_engines_angular_tables(gpu_available, filt, which)
 
 
 # ---------------------------------------------------------------- 3. mixed quads and the flag matrix
-ANG_KINDS = {"ang_h+": 6, "ang_h-": 27, "ang_v-": 41, "ang_v+": 60, "ang_18": 18, "ang_50": 50}
-PER_BAD_KIND = 12
-BAD_KINDS = ("unavailable", "pitch_low", "pitch_2", "offset_2", "frame", "mode_80", "mode_81", "mode_c3", "mode_ff")
-
-
-@lru_cache(maxsize=None)
-def _mixed_case():
-    w, h = 136, 72
-    frame = C.case(w, h, None)[0][1]
-    un = mipgpu.unavailable_cus(w, h)
-    assert [A.ANGLE[ANG_KINDS[k]] for k in ("ang_h+", "ang_h-", "ang_v-", "ang_v+")] == [20, -14, -14, 16]
-    assert [ANG_KINDS[k] < 34 for k in ("ang_h+", "ang_h-", "ang_v-", "ang_v+")] == [True, True, False, False]
-    rng = np.random.default_rng(0x4A)
-    cus = P.sample_cus(w, h, un, seed=0x4A, per_shape=1)
-    shape, _, _, bw, bh = layout.cu_geometry(w, h, cus)
-    small = bw * bh <= 64
-    assert small.any() and (~small).any()
-    good = ["mip", "planar", "dc"] + list(ANG_KINDS)
-    kind, cu = [], []
-    for k in good:
-        kind += [k] * cus.size
-        cu += list(cus)
-    wide = cus[bw >= 16]
-    for k in BAD_KINDS:
-        for j in range(PER_BAD_KIND):
-            kind.append(k)
-            cu.append(int(rng.choice(np.nonzero(un)[0]) if k == "unavailable" else rng.choice(wide) if k == "pitch_low" else rng.choice(cus)))
-    kind, cu = np.array(kind), np.array(cu, np.int64)
-    for seed in range(256):                                   # a shuffle that puts every kind into every quad position
-        order = np.random.default_rng(seed).permutation(cu.size)
-        if all(set(kind[order][p::4]) == set(kind) for p in range(4)):
-            break
-    else:
-        raise AssertionError("no shuffle mixes the kinds over the quad positions")
-    kind, cu = kind[order], cu[order]
-    last = layout.cu_geometry(w, h, cus)[3].argmax()          # the list ends with a large angular item that is
-    kind, cu = np.append(kind, "past_end"), np.append(cu, cus[last])   # one sample too long for `out`
-    gshape = layout.cu_geometry(w, h, cu)[0]
-    mode = np.zeros(cu.size, np.int64)
-    for i, k in enumerate(kind):
-        if k == "mip":
-            mode[i] = rng.integers(0, layout.SHAPES[gshape[i]].total_modes)
-        elif k in ("planar", "dc"):
-            mode[i] = REGULAR[k == "dc"]
-        elif k in ANG_KINDS:
-            mode[i] = BASE + ANG_KINDS[k]
-        else:                                                 # rejected entries carry every kind of valid mode
-            mode[i] = (BASE + 34, BASE + 2, REGULAR[0], 1)[i % 4] if k != "past_end" else BASE + 23
-    items, total = mipgpu.pred_items(w, h, 0, cu, mode)
-    items["pitch"][kind == "pitch_low"] = 8
-    items["pitch"][kind == "pitch_2"] += 2
-    items["offset"][kind == "offset_2"] += 2
-    items["frame"][kind == "frame"] = 1                       # == nframes of the call
-    for k, code in (("mode_80", 0x80), ("mode_81", 0x81), ("mode_c3", 0xC3), ("mode_ff", 0xFF)):
-        items["mode"][kind == k] = code
-    return w, h, frame, un, cus, kind, cu, items, total
+_mixed_case = V.mixed_case
 
 
 def test_mixed_quads_and_the_flag_matrix(gpu_available):
@@ -338,20 +233,8 @@ def test_frame_layout_with_a_pitch_that_is_no_multiple_of_8(gpu_available, w, h)
     row.  A set of CUs of mixed shapes that do not overlap, one launch, modes cycling through all 65."""
     import torch
     assert w % 8 == 4
-    frame = C.frames(w, h, 2)[1]
-    un = mipgpu.unavailable_cus(w, h)
-    cand = P.sample_cus(w, h, un, seed=w, per_shape=10)
-    cand = cand[np.random.default_rng(w).permutation(cand.size)]
-    shape, x, y, bw, bh = layout.cu_geometry(w, h, cand)
-    used, keep = np.zeros((h, w), bool), []
-    for i in range(cand.size):
-        if x[i] + bw[i] <= w and not used[y[i]:y[i] + bh[i], x[i]:x[i] + bw[i]].any():
-            used[y[i]:y[i] + bh[i], x[i]:x[i] + bw[i]] = True
-            keep.append(i)
-    keep = np.array(keep)
-    cus, shape, x, y, bw, bh = cand[keep], shape[keep], x[keep], y[keep], bw[keep], bh[keep]
+    frame, cus, shape, x, y, bw, bh, modes, used = V.narrow_case(w, h)
     assert len(set(shape)) >= 12 and (bw >= 8).any() and (bw == 4).any() and used.mean() > 0.5
-    modes = 2 + (np.arange(cus.size) * 7) % 65
     assert set(modes) == set(range(2, 67))
     want = angular_blocks(frame, w, h, cus)
     items, n_out = mipgpu.pred_items(w, h, 0, cus, BASE + modes, layout="frame", nframes=1)
@@ -377,14 +260,8 @@ def test_packed_list_of_4_wide_cus(gpu_available):
     """Packed 4-wide blocks (pitch 4): 8-byte stores of whole rows, four small blocks per wave step
     and the whole-wave path (4x32) in one list."""
     import torch
-    w, h = 136, 72
-    frame = C.case(w, h, None)[0][2]
-    un = mipgpu.unavailable_cus(w, h)
-    cus = P.sample_cus(w, h, un, seed=0x77, per_shape=4)
-    shape, x, y, bw, bh = layout.cu_geometry(w, h, cus)
-    cus, bh = cus[bw == 4], bh[bw == 4]
+    w, h, frame, cus, bh, modes = V.four_wide_case()
     assert set(bh) == {4, 8, 16, 32}
-    modes = 2 + (np.arange(cus.size) * 11) % 65
     want = angular_blocks(frame, w, h, cus)
     items, total = mipgpu.pred_items(w, h, 0, cus, BASE + modes)
     assert np.all(items["pitch"] == 4)
@@ -514,52 +391,18 @@ def test_multipass_scan(gpu_available):
     one) next to MIP and Planar items that the first kernel emits.  The list's last entry, in a
     partial row, is an angular item."""
     import torch
-    w, h = 136, 72
-    frame = C.case(w, h, None)[0][0]
-    un = mipgpu.unavailable_cus(w, h)
-    n = L.multipass_work(L.ENTRIES_PER_ROUND)
-    rows = -(-n // L.ENTRIES_PER_WAVE)
+    m = V.multipass_list()
+    w, h, frame, n, rows, items, total = (m[k] for k in ("w", "h", "frame", "n", "rows", "items", "total"))
+    bw, bh, busy, ang_pos, per_row, at, which, kind = (m[k] for k in ("bw", "bh", "busy", "ang_pos", "per_row", "at", "which", "kind"))
+    assert n == L.multipass_work(L.ENTRIES_PER_ROUND) and rows == -(-n // L.ENTRIES_PER_WAVE)
     assert n < 1 << 20 and n % L.ENTRIES_PER_WAVE and L.passes(rows, L.ROWS_PER_ROUND) == (2, 3)
-    rng = np.random.default_rng(0x6D)
-    cus = P.sample_cus(w, h, un, seed=0x6D, per_shape=1)
-    shape, x, y, bw, bh = layout.cu_geometry(w, h, cus)
-    pick = np.concatenate([rng.choice(np.nonzero(bw * bh <= 64)[0], 24), rng.choice(np.nonzero((bw * bh > 64) & (bw * bh <= 512))[0], 8)])
-    cus, shape, x, y, bw, bh = cus[pick], shape[pick], x[pick], y[pick], bw[pick], bh[pick]
-    table_modes = (2, 18, 29, 34, 45, 50, 66)
-    ang_want = angular_blocks(frame, w, h, cus, table_modes)
-    reg_want = regular_blocks(frame, w, h, cus)
-    # positions: one angular item per row, six more in every 97th row, the last entry; then MIP / Planar items elsewhere
-    pos = np.arange(rows) * L.ENTRIES_PER_WAVE + (np.arange(rows) * 7) % L.ENTRIES_PER_WAVE
-    pos[-1] = n - 1
-    busy = np.arange(0, rows - 1, 97)
-    extra = (busy[:, None] * L.ENTRIES_PER_WAVE + (busy[:, None] * 7 + 1 + 9 * np.arange(6)[None, :]) % L.ENTRIES_PER_WAVE).reshape(-1)
-    ang_pos = np.unique(np.concatenate([pos, extra]))
     assert ang_pos.max() == n - 1 and ang_pos.size == rows + busy.size * 6
-    per_row = np.bincount(ang_pos // L.ENTRIES_PER_WAVE, minlength=rows)
     assert per_row.min() >= 1 and per_row.max() == 7
     wave = np.arange(rows) % L.ROWS_PER_ROUND                                # every wave emits in at least two passes
     assert np.bincount(wave, weights=per_row > 0, minlength=L.ROWS_PER_ROUND).min() >= 2
-    free = np.setdiff1d(np.arange(n), ang_pos)
-    other_pos = rng.choice(free, 3000, replace=False)
-    at = np.concatenate([ang_pos, other_pos])
-    order = np.argsort(at)
-    which = rng.integers(0, cus.size, at.size)
-    kind = np.concatenate([np.zeros(ang_pos.size, int), rng.integers(1, 3, other_pos.size)])   # 0 angular, 1 MIP, 2 Planar
-    slot = rng.integers(0, len(table_modes), at.size)
-    mode = np.where(kind == 0, BASE + np.array(table_modes)[slot], np.where(kind == 1, 0, I.MODE_PLANAR))
-    at, which, kind, slot, mode = at[order], which[order], kind[order], slot[order], mode[order]
-    real, total = mipgpu.pred_items(w, h, 0, cus[which], mode)
-    items = np.zeros(n, mipgpu.PRED_ITEM)
-    items[:] = PADDING
-    items[at] = real
     small = (bw * bh <= 64)[which]
     assert (small & (kind == 0)).any() and (~small & (kind == 0)).any() and at.size < n // 20   # a minority of the entries
-    expect = np.full(total + 64, FILL, np.uint16)
-    mip = {i: P.CuPredictor(frame, x[i], y[i], shape[i]).predict(0) for i in range(cus.size)}
-    for i in range(at.size):
-        c = which[i]
-        blk = ang_want[int(cus[c])][slot[i]] if kind[i] == 0 else mip[c] if kind[i] == 1 else reg_want[int(cus[c])][0]
-        expect[real["offset"][i]:real["offset"][i] + bw[c] * bh[c]] = blk.reshape(-1)
+    expect = V.multipass_expected(m, V.DEFAULT)
     with MipEngine(w, h) as eng:
         out = _sentinel(total + 64)
         sk = torch.zeros(1, dtype=torch.int32, device="cuda")
